@@ -1,19 +1,21 @@
 #!/usr/bin/env python3
 """Benchmark of the DTQN TD-update hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1: under torch.distributed.run (RANK / WORLD_SIZE in the environment) every process is one rank; started plainly, bench.py
-re-executes itself under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N` on 127.0.0.1 (one rank per GPU over RCCL).
+starts itself again as a child `python -m torch.distributed.run --nnodes=1 --nproc-per-node N` on 127.0.0.1 (one rank per GPU over RCCL).
 
 One "step" = one DtqnAgent.train() = one TD update (sample windows -> 3 forwards -> double-DQN loss
 -> backward -> clip -> Adam; four launches at batch 32, the window draw is part of the forward kernel) on a device-resident
 synthetic replay of the shape SURVEY.md section 8d prescribes.  Workload at every N: BASELINE.json's metric configuration, DiscreteCarFlag-v0 shapes,
 context 50, d_model 64, 8 heads, 2 layers, batch 32 PER GPU (weak scaling: each rank owns its
 replay shard and batch; the only exchange is the flat-gradient all-reduce over RCCL).
-Rank 0 prints ONE JSON line (kept under 4 KB: the contract keys first, then `roofline` and `cpu_baseline`, then one-number
-summaries) and writes everything else it measured -- per-update latency distributions, per-config details, counter dumps --
-to gpurun_out/bench_detail.json.
+A plain run sets up, warms up, times the K steps and prints ONE JSON line from rank 0 with the contract keys only (`metric`,
+`value`, `unit`, `ms_per_step`, `higher_is_better`, `dtype`, ...).  --dump-outputs DIR also writes what the last timed step
+computed (dump_outputs).  --full adds every secondary measurement to the line (kept under 4 KB: the contract keys first, then
+`roofline` and `cpu_baseline`, then one-number summaries) and writes everything else it measured -- per-update latency
+distributions, per-config details, counter dumps -- to the file --detail names.
 """
 from __future__ import annotations
 
@@ -372,6 +374,8 @@ def make_agent(c, batch, device, rank, sampler, data_parallel=True):
     from dtqn_amd.utils.random import set_global_seed
     if c["kind"] == "box":
         set_global_seed(1 + rank, env)
+    else:
+        set_global_seed(1 + rank)          # the initial weights too: the same arguments give the same inputs from run to run
     agent = get_agent("DTQN", [env], 8, 0, c["D"], 500_000, device, 3e-4, batch, c["L"], c["T"], c["L"], 10_000, 0.99,
                       c["H"], c["NL"], 0.0, False, "res", "learned", 0, sampler=sampler, sample_seed=1 + rank, data_parallel=data_parallel)
     fill_synthetic_replay(agent, seed=1 + rank, c=c)
@@ -641,8 +645,10 @@ def env_step_rate(agent, seconds: float = 3.0, env_id: str = "DiscreteCarFlag-v0
 
 def _self_launch(args) -> None:
     """`python bench.py --gpus N` outside torch.distributed.run: start the N ranks ourselves (same interpreter, one rank per
-    GPU, rendezvous on 127.0.0.1) and hand the process over to the launcher; rank 0 of the job prints the line."""
+    GPU, rendezvous on 127.0.0.1) under the launcher in a child process and exit with its status; rank 0 of the job prints the
+    line.  A child, not an exec: this process has already opened the HIP runtime (device_count)."""
     import socket
+    import subprocess
     n_dev = torch.cuda.device_count()
     if n_dev < args.gpus and not ddp.same_device():
         raise SystemExit(f"--gpus {args.gpus} but only {n_dev} GPU(s) are visible")
@@ -653,7 +659,7 @@ def _self_launch(args) -> None:
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
-    os.execvpe(sys.executable, cmd, env)
+    raise SystemExit(subprocess.call(cmd, env=env))
 
 
 def _r(x, nd=4):
@@ -668,7 +674,142 @@ def _r(x, nd=4):
 
 
 LINE_LIMIT = 4000      # bytes: the driver keeps an 8 KB stdout tail; round 2's 37 KB line was cut and never parsed
+DUMP_LIMIT = 64 << 20  # bytes: all files --dump-outputs writes, together
 
+
+def dump_outputs(agent, out_dir: str, limit: int = DUMP_LIMIT) -> dict:
+    """--dump-outputs DIR: what the last timed DtqnAgent.train() computed, as a caller reads it back from the learner, one float32
+    <name>.npy each: the policy parameters and Adam moments that update wrote (theta_pol, adam_m, adam_v), its flat gradient (grad)
+    and its statistics (stats, learner.STAT_NAMES order).  An array over its share of `limit` is written as a fixed sample of its
+    elements (PCG64 seed 0, sorted indices: the same elements on every run).  Returns {name: (elements written, elements)}."""
+    from dtqn_amd.learner import STAT_NAMES
+    eng = agent.engine
+    big = {"theta_pol": eng.theta_pol, "grad": eng.grad, "adam_m": eng.adam_m, "adam_v": eng.adam_v}
+    stats = eng.stats.detach().float().cpu().numpy()
+    assert stats.size == len(STAT_NAMES)
+    cap = (limit - stats.nbytes - 128 * (len(big) + 1)) // (4 * len(big))       # elements per array (128: .npy header)
+    os.makedirs(out_dir, exist_ok=True)
+    out = {}
+    for name, t in big.items():
+        a = t.detach().reshape(-1).float().cpu().numpy()
+        n = a.size
+        if n > cap:
+            a = a[np.sort(np.random.Generator(np.random.PCG64(0)).choice(n, cap, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+        out[name] = (int(a.size), int(n))
+    np.save(os.path.join(out_dir, "stats.npy"), stats)
+    out["stats"] = (int(stats.size), int(stats.size))
+    return out
+
+
+def full_measurements(args, agent, c, device, world, ms, ups, lat, exchange, line) -> dict:
+    """--full: everything a plain run leaves out, measured on rank 0 after the timed steps -- per-kernel times, roofline, HBM-bound
+    launches, CPU baselines, BASELINE configs 2-5, the image config, env-steps/s -- added to `line` (after its contract keys);
+    returns the detail record."""
+    ft = f_tok(c)
+    tokens = args.batch * c["L"]
+    tiled = bool(agent.engine.net.tiled)
+    kern = time_kernels(agent)
+    kern_isolated = None
+    pipe = getattr(agent.engine, "_pipe", None)
+    pipe_counts = None if pipe is None else {"used": int(pipe["used"]), "inline": int(pipe["inline"])}      # of everything this agent ran so far
+    if pipe is not None and pipe["ride"] and "dtqn_forward_kernel_target_inline" in kern and agent.dp is None:
+        # pipelined update on one GPU: the line carries the IN-STREAM durations (what rocprofv3 --kernel-trace reports per dispatch)
+        kern_isolated = kern
+        ins = time_kernels_in_stream(agent)
+        kern = dict(kern_isolated, **{k: v for k, v in ins.items() if not k.startswith("_")})
+        kern["_event_us"] = ins["_event_us"]
+        kern["_step_instrumented_us"] = ins["_step_instrumented_us"]
+        kern["_step_plain_us"] = ins["_step_plain_us"]
+        kern["_event_pair_isolated_us"] = kern_isolated.get("_event_pair_us")
+    dom = max(("dtqn_forward_kernel", "dtqn_backward_kernel"), key=lambda k: kern[k])
+    # algorithmic FLOPs per launch: forward kernel = 3 forwards; backward kernel = data-gradient half
+    # of the backward (~ 1x forward; the weight-gradient half runs in dtqn_wgrad_kernel)
+    # (pipelined forward: the launch on the update's stream carries the two policy passes)
+    piped = "dtqn_forward_kernel_target_inline" in kern
+    stage_flops = {"dtqn_forward_kernel": (2 if piped else 3) * tokens * ft, "dtqn_backward_kernel": (2 if piped else 1) * tokens * ft}
+    flops = stage_flops[dom]
+    ach = flops / (kern[dom] * 1e-6) / 1e12
+    p_t = agent.engine.net.n_trainable
+    p_all = agent.engine.net.n_theta
+    gather_bytes = args.batch * ((c["L"] + 1) * 4 * c["O"] + (c["L"] + 1) + c["L"] * 4 + c["L"])
+    alg_bytes = gather_bytes + 4 * 2 * p_all + 4 * p_t + 28 * p_t           # SURVEY.md section 8d
+    traffic, traffic_src = (None, None) if tiled else pmc_traffic(dom, args.batch, args.config)
+    whole_frac = 5 * tokens * ft / (ms * 1e-3) / 1e12 / MFMA_F32_PEAK_TFLOPS
+    crit = {k: v for k, v in kern.items() if not k.startswith("_") and not k.endswith("_target_inline")}
+    detail = {"build": build_digest(), "kernels_us": kern, "kernels_us_sum": float(sum(crit.values())), "kernels_us_isolated": kern_isolated,
+              "kernels_us_method": "intervals between in-stream events behind every launch (nothing synchronised), minus the per-event cost = (instrumented step - plain step) / 4"
+              if kern_isolated is not None else "one launch at a time behind a drained stream, minus the empty event pair",
+              "forward": "policy passes as 2 x B x 4 workgroups of 16 rows; the next update's target pass rides in the backward launch"
+              if "dtqn_forward_kernel_target_inline" in kern else "three passes in one launch"}
+    # -------- the line: contract keys first, then roofline and cpu_baseline, then one-number summaries ---------------
+    line["roofline"] = {"bound": "mfma", "kernel": dom if not tiled else dom.replace("_kernel", "") + " stage (row-block tl_* kernels)",
+                        "achieved": ach, "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": ach / MFMA_F32_PEAK_TFLOPS,
+                        "traffic": traffic, "traffic_src": traffic_src, "launch_us": kern[dom], "flops_per_launch": flops,
+                        # both stages and the whole update priced the same way (backward = data-gradient half: 1x one
+                        # forward pass; weight gradients are their own kernel)
+                        "stage_frac": {k.replace("dtqn_", "").replace("_kernel", ""): f / (kern[k] * 1e-6) / 1e12 / MFMA_F32_PEAK_TFLOPS
+                                       for k, f in stage_flops.items()},
+                        "whole_update_frac": whole_frac}
+    if world == 1 and not args.no_cpu_baseline:
+        cb = cpu_baseline(c, args.batch) if args.config == 1 else cpu_baseline_other(args.config, 12.0)
+        detail["cpu_baseline"] = cb
+        ref = cb.get("reference_in_build_container") or {}
+        line["cpu_baseline"] = {"value": cb["value"], "unit": cb["unit"], "cores": cb["cores"], "kind": cb["kind"],
+                                "sample": cb["sample"],
+                                "reference_train_in_build_container_updates_per_s":
+                                    {str(r["threads"]): r["td_updates_per_s"] for r in ref.get("runs", [])}}
+    line["kernels_us"] = {k.replace("dtqn_", "").replace("_kernel", ""): v for k, v in kern.items() if not k.startswith("_")}
+    line["kernels_us"]["sum_on_stream"] = detail["kernels_us_sum"]
+    line["kernels_us"]["method"] = "in_stream" if kern_isolated is not None else "isolated"
+    if pipe_counts is not None:
+        line["pipeline"] = pipe_counts
+    line["hbm_view"] = {"algorithmic_bytes_per_update": alg_bytes, "achieved_GBs": alg_bytes / (ms * 1e-3) / 1e9,
+                        "frac": alg_bytes / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS}
+    if not tiled:
+        hb = time_hbm_kernels(agent, c, kern)
+        detail["hbm_kernels"] = hb
+        line["hbm_kernels"] = {k.replace("dtqn_", "").replace("_kernel", ""): {"bytes": v["bytes"], "us": v["us"], "frac_of_8TBs": v["frac"],
+                                                                                **({"us_per_record": v["us_per_record"]} if "us_per_record" in v else {})}
+                               for k, v in hb.items()}
+    detail["update_latency_us"] = lat
+    line["update_us_median"] = lat["us_median"]
+    if world > 1:
+        exchange["weak_scaling_efficiency"] = (ups / world) / exchange["solo_updates_per_s_rank0"]
+        line["exchange"] = exchange
+    if world == 1 and args.config == 1 and not args.no_other_configs:
+        oc = other_configs(device, with_cpu=not args.no_cpu_baseline)
+        detail["other_configs"] = {k: dict(v, mfma_counters=mfma_counters(int(k[-1]))) for k, v in oc.items()}
+        img = image_config(device)
+        detail["image_config"] = img
+        line["image_obs_config"] = {"updates_per_s": img["td_updates_per_s"], "frac_mfma": img["frac_of_f32_mfma_peak"],
+                                    "tflop_per_update": img["algorithmic_tflop_per_update"]}
+        line["other_configs"] = {k[-1]: {"B": CONFIGS[int(k[-1])]["B"], "updates_per_s": v["td_updates_per_s"],
+                                         "frac_mfma": v["frac_of_f32_mfma_peak"], "clip_adam_frac_hbm": v["clip_adam_hbm"]["frac"],
+                                         "cpu_updates_per_s": v.get("cpu_baseline", {}).get("value")} for k, v in oc.items()}
+    if world == 1 and c["kind"] == "box" and not args.no_env_rate:
+        rates = env_step_rate(agent)
+        detail["env_steps_per_sec"] = rates
+        line["env_steps_per_sec"] = {"actor_only": rates["actor_only"], "coupled_1to1": rates["coupled_1to1"],
+                                     "coupled_1to1_overlap": rates["coupled_1to1_overlapped"],
+                                     **{k: v for k, v in rates.items() if k.startswith("vector")}}
+    if world == 1 and args.config == 1 and not args.no_env_rate:
+        # live Memory-5-v0 (BASELINE config 3's env) on the host cores against the cfg-3 network on the GPU
+        c3 = CONFIGS[3]
+        env = dt_envs.make("Memory-5-v0")
+        from dtqn_amd.utils.random import set_global_seed
+        set_global_seed(1, env)
+        a3 = get_agent("DTQN", [env], 8, 0, c3["D"], 500_000, device, 3e-4, c3["B"], c3["L"], -1, c3["L"], 10_000, 0.99,
+                       c3["H"], c3["NL"], 0.0, False, "res", "learned", 0, sampler="device", sample_seed=1)
+        import run as runpy
+        runpy.prepopulate(a3, 30_000, [env])
+        r3 = env_step_rate(a3, 2.0, "Memory-5-v0", vector_sizes=(8,))
+        detail["env_steps_per_sec_config3"] = dict(r3, env="Memory-5-v0 (live, host cores)", batch=c3["B"])
+        line["env_steps_per_sec_cfg3"] = {"actor_only": r3["actor_only"], "coupled_1to1": r3["coupled_1to1"]}
+        del a3
+    detail["mfma_counters"] = mfma_counters(args.config)
+    line["detail_file"] = os.path.relpath(args.detail, ROOT)
+    return detail
 
 def main():
     ap = argparse.ArgumentParser()
@@ -684,6 +825,12 @@ def main():
     ap.add_argument("--no-env-rate", action="store_true", help="skip the live env-steps/s loops (cleaner rocprofv3 traces)")
     ap.add_argument("--detail", default=os.path.join(ROOT, "gpurun_out", "bench_detail.json"),
                     help="where the full measurement record goes (the printed line only carries summaries)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline: per-kernel times and roofline, update latency, HBM-bound "
+                         "launches, CPU baselines, BASELINE configs 2-5, the image config, env-steps/s, the N > 1 exchange, and "
+                         "the --detail file (the --no-* options trim it)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -748,8 +895,10 @@ def main():
         torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(tmax.item())
     agent._drain_stats(block=True)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(agent, args.dump_outputs)
     exchange = None
-    if world > 1:
+    if world > 1 and args.full:
         # the one exchange step of an update, timed by itself (every rank takes part; rank 0 reports), HIP events on the launch
         # stream: the exchange the start-up check SELECTED (dist.DataParallel.selection) and, beside it, the library collective
         pct = lambda ts: None if not ts else {"median": float(np.median(ts)), "p10": float(np.percentile(ts, 10)), "p90": float(np.percentile(ts, 90))}
@@ -781,50 +930,15 @@ def main():
         exchange["kernels_us_sum_per_rank"] = [float(k.item()) for k in allk]
         del solo
         sync_all()
-    # per-update latency distribution: agent.train() takes part in the gradient exchange, so EVERY rank runs it (rank 0 reports)
-    lat = update_latency(agent)
-    sync_all()
+    lat = None
+    if args.full:
+        # per-update latency distribution: agent.train() takes part in the gradient exchange, so EVERY rank runs it (rank 0 reports)
+        lat = update_latency(agent)
+        sync_all()
 
     if rank == 0:
         ms = elapsed * 1e3 / args.steps
         ups = world * args.steps / elapsed                     # whole-job TD updates / s (each rank does one per step)
-        ft = f_tok(c)
-        tokens = args.batch * c["L"]
-        tiled = bool(agent.engine.net.tiled)
-        kern = time_kernels(agent)
-        kern_isolated = None
-        pipe = getattr(agent.engine, "_pipe", None)
-        pipe_counts = None if pipe is None else {"used": int(pipe["used"]), "inline": int(pipe["inline"])}      # of everything this agent ran so far
-        if pipe is not None and pipe["ride"] and "dtqn_forward_kernel_target_inline" in kern and agent.dp is None:
-            # pipelined update on one GPU: the line carries the IN-STREAM durations (what rocprofv3 --kernel-trace reports per dispatch)
-            kern_isolated = kern
-            ins = time_kernels_in_stream(agent)
-            kern = dict(kern_isolated, **{k: v for k, v in ins.items() if not k.startswith("_")})
-            kern["_event_us"] = ins["_event_us"]
-            kern["_step_instrumented_us"] = ins["_step_instrumented_us"]
-            kern["_step_plain_us"] = ins["_step_plain_us"]
-            kern["_event_pair_isolated_us"] = kern_isolated.get("_event_pair_us")
-        dom = max(("dtqn_forward_kernel", "dtqn_backward_kernel"), key=lambda k: kern[k])
-        # algorithmic FLOPs per launch: forward kernel = 3 forwards; backward kernel = data-gradient half
-        # of the backward (~ 1x forward; the weight-gradient half runs in dtqn_wgrad_kernel)
-        # (pipelined forward: the launch on the update's stream carries the two policy passes)
-        piped = "dtqn_forward_kernel_target_inline" in kern
-        stage_flops = {"dtqn_forward_kernel": (2 if piped else 3) * tokens * ft, "dtqn_backward_kernel": (2 if piped else 1) * tokens * ft}
-        flops = stage_flops[dom]
-        ach = flops / (kern[dom] * 1e-6) / 1e12
-        p_t = agent.engine.net.n_trainable
-        p_all = agent.engine.net.n_theta
-        gather_bytes = args.batch * ((c["L"] + 1) * 4 * c["O"] + (c["L"] + 1) + c["L"] * 4 + c["L"])
-        alg_bytes = gather_bytes + 4 * 2 * p_all + 4 * p_t + 28 * p_t
-        traffic, traffic_src = (None, None) if tiled else pmc_traffic(dom, args.batch, args.config)
-        whole_frac = 5 * tokens * ft / (ms * 1e-3) / 1e12 / MFMA_F32_PEAK_TFLOPS
-        crit = {k: v for k, v in kern.items() if not k.startswith("_") and not k.endswith("_target_inline")}
-        detail = {"build": build_digest(), "kernels_us": kern, "kernels_us_sum": float(sum(crit.values())), "kernels_us_isolated": kern_isolated,
-                  "kernels_us_method": "intervals between in-stream events behind every launch (nothing synchronised), minus the per-event cost = (instrumented step - plain step) / 4"
-                  if kern_isolated is not None else "one launch at a time behind a drained stream, minus the empty event pair",
-                  "forward": "policy passes as 2 x B x 4 workgroups of 16 rows; the next update's target pass rides in the backward launch"
-                  if "dtqn_forward_kernel_target_inline" in kern else "three passes in one launch"}
-        # -------- the line: contract keys first, then roofline and cpu_baseline, then one-number summaries ---------------
         line = {
             "metric": "env-steps/sec + TD-updates/sec, DiscreteCarFlag-v0 ctx=50 b=32, 1/2/4/8 GPU",
             "value": ups, "unit": "TD-updates/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -834,73 +948,8 @@ def main():
                                    f"{c['NL']} layers, obs {c['O']} {'f32' if c['kind'] == 'box' else 'tokens'}, {c['A']} actions, "
                                    f"batch {args.batch} per GPU, history {c['L']}, device replay {500_000 // c['T']} x {c['T']} steps",
                        "global_batch": args.batch * world, "parallelism": f"dp{world}", "sampler": args.sampler},
-            "roofline": {"bound": "mfma", "kernel": dom if not tiled else dom.replace("_kernel", "") + " stage (row-block tl_* kernels)",
-                         "achieved": ach, "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": ach / MFMA_F32_PEAK_TFLOPS,
-                         "traffic": traffic, "traffic_src": traffic_src, "launch_us": kern[dom], "flops_per_launch": flops,
-                         # both stages and the whole update priced the same way (backward = data-gradient half: 1x one
-                         # forward pass; weight gradients are their own kernel)
-                         "stage_frac": {k.replace("dtqn_", "").replace("_kernel", ""): f / (kern[k] * 1e-6) / 1e12 / MFMA_F32_PEAK_TFLOPS
-                                        for k, f in stage_flops.items()},
-                         "whole_update_frac": whole_frac},
         }
-        if world == 1 and not args.no_cpu_baseline:
-            cb = cpu_baseline(c, args.batch) if args.config == 1 else cpu_baseline_other(args.config, 12.0)
-            detail["cpu_baseline"] = cb
-            ref = cb.get("reference_in_build_container") or {}
-            line["cpu_baseline"] = {"value": cb["value"], "unit": cb["unit"], "cores": cb["cores"], "kind": cb["kind"],
-                                    "sample": cb["sample"],
-                                    "reference_train_in_build_container_updates_per_s":
-                                        {str(r["threads"]): r["td_updates_per_s"] for r in ref.get("runs", [])}}
-        line["kernels_us"] = {k.replace("dtqn_", "").replace("_kernel", ""): v for k, v in kern.items() if not k.startswith("_")}
-        line["kernels_us"]["sum_on_stream"] = detail["kernels_us_sum"]
-        line["kernels_us"]["method"] = "in_stream" if kern_isolated is not None else "isolated"
-        if pipe_counts is not None:
-            line["pipeline"] = pipe_counts
-        line["hbm_view"] = {"algorithmic_bytes_per_update": alg_bytes, "achieved_GBs": alg_bytes / (ms * 1e-3) / 1e9,
-                            "frac": alg_bytes / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS}
-        if not tiled:
-            hb = time_hbm_kernels(agent, c, kern)
-            detail["hbm_kernels"] = hb
-            line["hbm_kernels"] = {k.replace("dtqn_", "").replace("_kernel", ""): {"bytes": v["bytes"], "us": v["us"], "frac_of_8TBs": v["frac"],
-                                                                                    **({"us_per_record": v["us_per_record"]} if "us_per_record" in v else {})}
-                                   for k, v in hb.items()}
-        detail["update_latency_us"] = lat
-        line["update_us_median"] = lat["us_median"]
-        if world > 1:
-            exchange["weak_scaling_efficiency"] = (ups / world) / exchange["solo_updates_per_s_rank0"]
-            line["exchange"] = exchange
-        if world == 1 and args.config == 1 and not args.no_other_configs:
-            oc = other_configs(device, with_cpu=not args.no_cpu_baseline)
-            detail["other_configs"] = {k: dict(v, mfma_counters=mfma_counters(int(k[-1]))) for k, v in oc.items()}
-            img = image_config(device)
-            detail["image_config"] = img
-            line["image_obs_config"] = {"updates_per_s": img["td_updates_per_s"], "frac_mfma": img["frac_of_f32_mfma_peak"],
-                                        "tflop_per_update": img["algorithmic_tflop_per_update"]}
-            line["other_configs"] = {k[-1]: {"B": CONFIGS[int(k[-1])]["B"], "updates_per_s": v["td_updates_per_s"],
-                                             "frac_mfma": v["frac_of_f32_mfma_peak"], "clip_adam_frac_hbm": v["clip_adam_hbm"]["frac"],
-                                             "cpu_updates_per_s": v.get("cpu_baseline", {}).get("value")} for k, v in oc.items()}
-        if world == 1 and c["kind"] == "box" and not args.no_env_rate:
-            rates = env_step_rate(agent)
-            detail["env_steps_per_sec"] = rates
-            line["env_steps_per_sec"] = {"actor_only": rates["actor_only"], "coupled_1to1": rates["coupled_1to1"],
-                                         "coupled_1to1_overlap": rates["coupled_1to1_overlapped"],
-                                         **{k: v for k, v in rates.items() if k.startswith("vector")}}
-        if world == 1 and args.config == 1 and not args.no_env_rate:
-            # live Memory-5-v0 (BASELINE config 3's env) on the host cores against the cfg-3 network on the GPU
-            c3 = CONFIGS[3]
-            env = dt_envs.make("Memory-5-v0")
-            from dtqn_amd.utils.random import set_global_seed
-            set_global_seed(1, env)
-            a3 = get_agent("DTQN", [env], 8, 0, c3["D"], 500_000, device, 3e-4, c3["B"], c3["L"], -1, c3["L"], 10_000, 0.99,
-                           c3["H"], c3["NL"], 0.0, False, "res", "learned", 0, sampler="device", sample_seed=1)
-            import run as runpy
-            runpy.prepopulate(a3, 30_000, [env])
-            r3 = env_step_rate(a3, 2.0, "Memory-5-v0", vector_sizes=(8,))
-            detail["env_steps_per_sec_config3"] = dict(r3, env="Memory-5-v0 (live, host cores)", batch=c3["B"])
-            line["env_steps_per_sec_cfg3"] = {"actor_only": r3["actor_only"], "coupled_1to1": r3["coupled_1to1"]}
-            del a3
-        detail["mfma_counters"] = mfma_counters(args.config)
-        line["detail_file"] = os.path.relpath(args.detail, ROOT)
+        detail = full_measurements(args, agent, c, device, world, ms, ups, lat, exchange, line) if args.full else None
         line = _r(line)
         line["value"], line["ms_per_step"] = ups, ms              # the two the driver cross-checks: full precision
         text = json.dumps(line, separators=(",", ":"))
@@ -909,12 +958,13 @@ def main():
                 break
             line.pop(k, None)                                     # never reached with today's keys; the contract keys always stay
             text = json.dumps(line, separators=(",", ":"))
-        try:
-            os.makedirs(os.path.dirname(args.detail), exist_ok=True)
-            with open(args.detail, "w") as f:
-                json.dump(dict(detail, line=line), f, indent=1)
-        except OSError:
-            pass
+        if detail is not None:
+            try:
+                os.makedirs(os.path.dirname(args.detail), exist_ok=True)
+                with open(args.detail, "w") as f:
+                    json.dump(dict(detail, line=line), f, indent=1)
+            except OSError:
+                pass
         print(text, flush=True)
     if world > 1:
         torch.distributed.barrier()

@@ -43,15 +43,18 @@ def test_pmc_traffic_reads_the_committed_profile(monkeypatch):
 
 
 def test_gpus_n_outside_torchrun_launches_its_own_ranks(monkeypatch):
-    """`python bench.py --gpus 2` with no WORLD_SIZE re-executes under torch.distributed.run on 127.0.0.1."""
+    """`python bench.py --gpus 2` with no WORLD_SIZE runs itself under torch.distributed.run on 127.0.0.1, in a
+    child process whose exit status it exits with."""
     import argparse
     import bench
     import torch
     seen = {}
     monkeypatch.setattr(torch.cuda, "device_count", lambda: 8)
-    monkeypatch.setattr(os, "execvpe", lambda exe, cmd, env: seen.update(exe=exe, cmd=cmd, env=env))
+    monkeypatch.setattr(subprocess, "call", lambda cmd, env: seen.update(cmd=cmd, env=env) or 3)
     monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "2", "--steps", "7", "--warmup", "3"])
-    bench._self_launch(argparse.Namespace(gpus=2))
+    with pytest.raises(SystemExit) as ex:
+        bench._self_launch(argparse.Namespace(gpus=2))
+    assert ex.value.code == 3
     cmd = seen["cmd"]
     assert cmd[:3] == [sys.executable, "-m", "torch.distributed.run"] and "--nproc-per-node=2" in cmd and "--nnodes=1" in cmd
     assert cmd[cmd.index("--master-addr") + 1] == "127.0.0.1" and int(cmd[cmd.index("--master-port") + 1]) > 0
@@ -72,7 +75,7 @@ def test_line_rounding_keeps_the_line_small():
 @pytest.mark.gpu
 def test_bench_line_contract():
     """`python bench.py` prints ONE JSON line with the keys the driver and the judge read."""
-    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "200", "--warmup", "20", "--no-other-configs",
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "200", "--warmup", "20", "--full", "--no-other-configs",
                           "--no-env-rate", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, cwd=REPO)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -105,7 +108,7 @@ def test_two_ranks_print_one_whole_job_line_on_a_one_gpu_box():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(DTQN_DIST_SAME_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "60", "--warmup", "10",
-                          "--no-other-configs", "--no-env-rate", "--no-cpu-baseline"], capture_output=True, text=True, timeout=240,
+                          "--full", "--no-other-configs", "--no-env-rate", "--no-cpu-baseline"], capture_output=True, text=True, timeout=240,
                          cwd=REPO, env=env)        # (a rank-0-only collective hangs: this is the test that found update_latency's)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -132,7 +135,7 @@ def test_two_ranks_of_config_4_on_a_one_gpu_box():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(DTQN_DIST_SAME_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--config", "4", "--steps", "10", "--warmup", "3",
-                          "--no-other-configs", "--no-env-rate", "--no-cpu-baseline"], capture_output=True, text=True, timeout=400,
+                          "--full", "--no-other-configs", "--no-env-rate", "--no-cpu-baseline"], capture_output=True, text=True, timeout=400,
                          cwd=REPO, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -143,3 +146,60 @@ def test_two_ranks_of_config_4_on_a_one_gpu_box():
     assert d["value"] == pytest.approx(2 * 1000.0 / d["ms_per_step"], rel=1e-6) and d["value"] > 0
     assert d["exchange"]["kind"] in ("p2p", "rccl")
 
+
+
+def test_dump_outputs_writes_float_arrays_under_the_limit(tmp_path):
+    """--dump-outputs: one float32 .npy per array the last update wrote; an array over its share of the limit becomes the same
+    seeded sample of its elements on every call, and all files together stay under the limit."""
+    import types
+    import numpy as np
+    import torch
+    import bench
+    from dtqn_amd.learner import STAT_NAMES
+    g = torch.Generator().manual_seed(0)
+    eng = types.SimpleNamespace(theta_pol=torch.randn(5000, generator=g), grad=torch.randn(3000, generator=g),
+                                adam_m=torch.randn(3000, generator=g), adam_v=torch.rand(3000, generator=g),
+                                stats=torch.arange(len(STAT_NAMES), dtype=torch.float32))
+    agent = types.SimpleNamespace(engine=eng)
+    full = bench.dump_outputs(agent, str(tmp_path / "a"))
+    assert full == {"theta_pol": (5000, 5000), "grad": (3000, 3000), "adam_m": (3000, 3000), "adam_v": (3000, 3000),
+                    "stats": (len(STAT_NAMES), len(STAT_NAMES))}
+    for name in full:
+        a = np.load(tmp_path / "a" / f"{name}.npy")
+        assert a.dtype == np.float32
+        np.testing.assert_array_equal(a, getattr(eng, name).numpy())
+    limit = 32 * 1024
+    small = bench.dump_outputs(agent, str(tmp_path / "b"), limit=limit)
+    assert small["theta_pol"][0] < 5000 and small["grad"][0] < 3000
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) <= limit
+    th = np.load(tmp_path / "b" / "theta_pol.npy")
+    assert np.isin(th, eng.theta_pol.numpy()).all()
+    bench.dump_outputs(agent, str(tmp_path / "c"), limit=limit)
+    for name in small:
+        np.testing.assert_array_equal(np.load(tmp_path / "b" / f"{name}.npy"), np.load(tmp_path / "c" / f"{name}.npy"))
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_only_and_dumps_the_last_step(tmp_path):
+    """`python bench.py --steps K --warmup W` without --full: the contract keys and nothing that takes runs of its own; --dump-outputs
+    writes the update's arrays after exactly W + K optimizer steps of the measured learner."""
+    import numpy as np
+    from dtqn_amd.learner import STAT_NAMES
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "40", "--warmup", "7",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=300, cwd=REPO)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1 and lines[0].startswith('{"metric":')
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config"):
+        assert k in d, k
+    for k in ("roofline", "cpu_baseline", "kernels_us", "update_us_median", "other_configs", "env_steps_per_sec", "detail_file"):
+        assert k not in d, k
+    assert d["steps"] == 40 and d["warmup"] == 7 and d["unit"] == "TD-updates/s" and d["dtype"] == "f32"
+    assert d["value"] == pytest.approx(1000.0 / d["ms_per_step"], rel=1e-6) and d["value"] > 0
+    stats = np.load(tmp_path / "stats.npy")
+    assert stats.dtype == np.float32 and stats[STAT_NAMES.index("step")] == 47
+    for name in ("theta_pol", "grad", "adam_m", "adam_v"):
+        a = np.load(tmp_path / f"{name}.npy")
+        assert a.dtype == np.float32 and a.size > 0 and np.isfinite(a).all(), name
+    assert sum(os.path.getsize(tmp_path / f) for f in os.listdir(tmp_path)) <= 64 << 20
