@@ -714,18 +714,19 @@ __device__ __forceinline__ int balanced_block(int wave, int nblocks, int nlive, 
 // One chunk of NT (<= 4) consecutive key tiles of one (head, query-tile) item; DIAG: the last tile of the chunk is
 // the diagonal one (keys s > t masked).  Scores live in the log2 domain (q is pre-scaled by hd^-0.5 * log2 e), so
 // every probability is one v_exp_f32.  The NT score tiles are independent MFMA chains and share ONE pair of
-// max / sum reductions across the four lane groups.
+// max / sum reductions across the four lane groups.  row_base: the key row that kbase / vbase point at (0 for a whole tile; the first
+// row of the staged key block in the key-blocked kernels) -- s_first stays absolute for the causal mask and the dropout keys.
 template <int HD, int NT, bool DIAG>
 __device__ __forceinline__ void attention_forward_chunk(const float* kbase, const float* vbase, int ld, int s_first, int trow,
                                                         const float (&qf)[HD / 4], float& m, float& l,
                                                         f32x4 (&acc)[(HD + 15) / 16][2], bool rescale, const Thr& t,
-                                                        const Drop& dr, int layer, int h) {
+                                                        const Drop& dr, int layer, int h, int row_base = 0) {
     constexpr int KS = HD / 4, CT = (HD + 15) / 16;
     f32x4 st[NT];
 #pragma unroll
     for (int u = 0; u < NT; ++u) {
         st[u] = zero4();
-        const float* kp = kbase + (s_first + u * 16 + t.i) * ld + t.kq * KS;
+        const float* kp = kbase + (s_first - row_base + u * 16 + t.i) * ld + t.kq * KS;
 #pragma unroll
         for (int s = 0; s < KS; ++s) st[u] = mfma16(kp[s], qf[s], st[u]);
     }
@@ -772,7 +773,7 @@ __device__ __forceinline__ void attention_forward_chunk(const float* kbase, cons
     for (int u = 0; u < NT; ++u)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const float* vp = vbase + (s_first + u * 16 + t.kq * 4 + r) * ld;
+            const float* vp = vbase + (s_first - row_base + u * 16 + t.kq * 4 + r) * ld;
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct) {
                 const int c = ct * 16 + t.i;

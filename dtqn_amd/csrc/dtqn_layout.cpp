@@ -126,13 +126,16 @@ extern "C" int dtqn_net_init(DtqnNet* net) {
     // the bag branch is composed from the row-block kernels: as many bag entries as the records have rows
     if (net->bag_size > 0 && (net->bag_size > LP || !(D == 64 || D == 128 || D == 256))) return DTQN_ERR_CONFIG;
     if (net->tiled) {
-        // tiled kernels: D in {64, 128, 256}, context up to 512 (north_star's bound) as long as the attention tile q | k | v | dO of ONE head
-        // fits LDS (the test below): head widths up to 16 at 257 .. 512 rows, up to 32 at 256; wider heads at long contexts would need the
-        // K-blocked attention loop (out of scope)
+        // tiled kernels: D in {64, 128, 256}, context up to 512 (north_star's bound).  The attention runs on the whole-head tile while
+        // q | k | v | dO of ONE head fits LDS (dtqn_attn_whole_tile: head widths up to 16 at 257 .. 512 rows, up to 32 at 256), and on
+        // the key-blocked kernels beyond it -- admitted for native (not width-padded) d_model 128 / 256 networks without a bag, heads of
+        // 32 .. 128 columns; d_model 64, padded and bag networks keep the whole-tile bound
         if (!(D == 64 || D == 128 || D == 256) || LP > 512) return DTQN_ERR_CONFIG;
-        const int hd = net->head_dim;                    // tl_attn_kernel / tl_attn_bwd_kernel instantiations
+        const int hd = net->head_dim;                    // tl_attn_kernel / tl_attn_bwd_kernel (and tl_attn_kb_*) instantiations
         if (!(hd == 4 || hd == 8 || hd == 16 || hd == 32 || hd == 64 || hd == 128)) return DTQN_ERR_CONFIG;
-        if (((size_t)LP * (4 * net->head_dim + 4) + 2 * (size_t)LP) * sizeof(float) > 160 * 1024) return DTQN_ERR_CONFIG;
+        if (!dtqn_attn_whole_tile(LP, hd) &&
+            !(net->d_real == 0 && net->bag_size == 0 && (D == 128 || D == 256) && (hd == 32 || hd == 64 || hd == 128)))
+            return DTQN_ERR_CONFIG;
     }
     if (A > DTQN_MAX_ACTIONS || (!net->tiled && net->kep > 3 * D)) return DTQN_ERR_CONFIG;
 

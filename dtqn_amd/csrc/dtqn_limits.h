@@ -1,13 +1,22 @@
 // Coverage limits of the per-sequence fused kernels (one workgroup holds a whole context tile
 // in LDS).  Anything beyond returns DTQN_ERR_CONFIG from dtqn_net_init.
 #pragma once
+#include <stddef.h>
 #define DTQN_MAX_LP 64          /* padded context rows held in LDS (ctx_len <= 64) */
 #define DTQN_MAX_D 128          /* d_model instantiations: 64, 128 (and 16/32 for tests) */
-#define DTQN_MAX_HEAD_DIM 128   /* 4 .. 128 in the row-block attention kernels (128: contexts up to 64 rows, the LDS tile of one head); the whole-sequence kernels: 8, 16 (and 32: dtqn_ws_lite) */
+#define DTQN_MAX_HEAD_DIM 128   /* 4 .. 128 in the row-block attention kernels (whole-head tile while it fits LDS, key-blocked beyond: dtqn_attn_whole_tile); the whole-sequence kernels: 8, 16 (and 32: dtqn_ws_lite) */
 #define DTQN_MAX_ACTIONS 64
 #define DTQN_MAX_BAG 256        /* bag entries (bag_size <= padded context <= 256, the row-block tiled path's limit) */
 #define DTQN_THREADS 256        /* 4 wave64 per workgroup */
 #define DTQN_WAVES 4
+
+// Row-block attention (dtqn_tiled.hip): the whole-tile kernels hold ONE head's rows in LDS -- the forward q | k | v, the backward
+// q | k | v | dO plus the lse and delta rows.  A context whose backward tile exceeds 160 KB runs the key-blocked kernels instead
+// (tl_attn_kb_*: 64 rows of k | v or q | dO at a time); dtqn_net_init admits those shapes only where the key-blocked kernels are meant to run.
+static inline size_t dtqn_attn_tile_lds(int lp, int hd, int bwd) {
+    return bwd ? ((size_t)lp * (4 * hd + 4) + 2 * (size_t)lp) * sizeof(float) : (size_t)lp * (3 * hd + 4) * sizeof(float);
+}
+static inline int dtqn_attn_whole_tile(int lp, int hd) { return dtqn_attn_tile_lds(lp, hd, 1) <= 160 * 1024; }
 
 // The whole-sequence kernels exist as explicit instantiations <d_model, 16-row tiles, head_dim, waves> (dtqn_forward.hip:
 // dispatch_fwd, dtqn_backward.hip: td_backward): X(d, mt, hd, nw).  TRAIN = forward and backward exist; the first entry of a

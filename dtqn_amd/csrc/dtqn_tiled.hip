@@ -2048,6 +2048,293 @@ __global__ __launch_bounds__(256) void tl_attn_bwd_kernel(TlAttnBwdArgs a) {
     }
 }
 
+// ---- key-blocked attention (contexts whose whole-head tile does not fit LDS: dtqn_attn_whole_tile) ------------------------------------
+// The arithmetic of the whole-tile MFMA kernels above, with K | V (forward, dq) or q | dO (dk | dv) staged 64 rows at a time instead of
+// resident.  A 64-row block is exactly one 4-tile key chunk of attention_forward_mfma and the 16-row tiles are visited in the same order as
+// attention_backward_group_mfma's two passes, so at head widths of 16 and more (where the whole-tile kernels run on the matrix core too)
+// every sum is formed in the same order: the same bits.  Wave w of a workgroup owns 16-row tile w of its 64-row block.
+constexpr int TL_KB = 64;                              // rows of a query / key block (= TROWS: the records are TL_KB-row padded)
+// grid (S, H, LPB / 64): query block nqb - 1 - z (the long blocks of the causal triangle start first)
+template <int HD, bool DROP>
+__global__ __launch_bounds__(256) void tl_attn_kb_kernel(TlAttnArgs a) {
+    constexpr int LDK = 2 * HD + 4, KS = HD / 4, CT = (HD + 15) / 16;
+    __shared__ __attribute__((aligned(16))) float KV[TL_KB * LDK];     // [64][k | v] of this head
+    const Thr t = make_thr();
+    const int s = (int)blockIdx.x, h = (int)blockIdx.y, qb = a.lpb / TL_KB - 1 - (int)blockIdx.z;
+    const int ti = qb * 4 + t.wave, trow = ti * 16 + t.i;
+    const int last_tile = (a.n - 1) / 16;
+    float* op = frow(a.o, s, trow) + h * HD;
+    float* lse = a.lse.base != nullptr ? a.lse.base + (size_t)s * a.lse.stride + (size_t)h * a.lpb : nullptr;
+    if (qb * 4 > last_tile) {                                          // pad rows only: o = 0, lse = 0
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct)
+            if (ct * 16 + t.kq * 4 < HD) st4(op + ct * 16 + t.kq * 4, make_float4(0.f, 0.f, 0.f, 0.f));
+        if (lse != nullptr && t.kq == 0) lse[trow] = 0.f;
+        return;
+    }
+    const bool live_tile = ti <= last_tile;
+    const float scale = 1.4426950408889634f / sqrtf(a.hd_eff);         // hd^-0.5 * log2(e), as attention_forward_mfma
+    float qf[KS];
+    const float* qp = frow(a.qkv, s, trow) + h * HD + t.kq * KS;
+#pragma unroll
+    for (int c = 0; c < KS; ++c) qf[c] = live_tile ? qp[c] * scale : 0.f;
+    f32x4 acc[CT][2];
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) { acc[ct][0] = zero4(); acc[ct][1] = zero4(); }
+    float m = -INFINITY, l = 0.f;
+    Drop dr = drop_off();
+    if constexpr (DROP) dr = tl_drop(a.drop, s);
+    for (int kb = 0; kb <= qb; ++kb) {
+        if (kb > 0) __syncthreads();                                   // every wave is done with the previous block
+        for (int idx = t.tid; idx < TL_KB * 2 * (HD / 4); idx += 256) {
+            const int r = idx / (2 * (HD / 4)), rem = idx - r * (2 * (HD / 4));
+            const int which = rem / (HD / 4), c = (rem - which * (HD / 4)) * 4;
+            st4(KV + r * LDK + which * HD + c, ld4(frow(a.qkv, s, kb * TL_KB + r) + (1 + which) * a.D + h * HD + c));
+        }
+        __syncthreads();
+        if (!live_tile) continue;
+        const int s0 = kb * TL_KB;
+        if (kb < qb) {
+            attention_forward_chunk<HD, 4, false>(KV, KV + HD, LDK, s0, trow, qf, m, l, acc, kb > 0, t, dr, a.layer, h, s0);
+        } else {
+            switch (t.wave) {                                          // the diagonal block: tiles 0 .. w of it
+                case 0: attention_forward_chunk<HD, 1, true>(KV, KV + HD, LDK, s0, trow, qf, m, l, acc, kb > 0, t, dr, a.layer, h, s0); break;
+                case 1: attention_forward_chunk<HD, 2, true>(KV, KV + HD, LDK, s0, trow, qf, m, l, acc, kb > 0, t, dr, a.layer, h, s0); break;
+                case 2: attention_forward_chunk<HD, 3, true>(KV, KV + HD, LDK, s0, trow, qf, m, l, acc, kb > 0, t, dr, a.layer, h, s0); break;
+                default: attention_forward_chunk<HD, 4, true>(KV, KV + HD, LDK, s0, trow, qf, m, l, acc, kb > 0, t, dr, a.layer, h, s0); break;
+            }
+        }
+    }
+    // lane (i, kq) holds O^T[c = ct*16 + kq*4 + e][trow]
+    const bool live = live_tile && trow < a.n;
+    const float inv = live ? 1.0f / l : 0.f;
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) {
+        const int c = ct * 16 + t.kq * 4;
+        if (c < HD)
+            st4(op + c, make_float4((acc[ct][0][0] + acc[ct][1][0]) * inv, (acc[ct][0][1] + acc[ct][1][1]) * inv,
+                                    (acc[ct][0][2] + acc[ct][1][2]) * inv, (acc[ct][0][3] + acc[ct][1][3]) * inv));
+    }
+    if (lse != nullptr && t.kq == 0) lse[trow] = live ? m * 0.6931471805599453f + __logf(l) : 0.f;
+}
+
+// delta = rowsum(dO o) of rows [row0, row0 + 64) and their lse -> LDS (tl_attn_bwd_kernel's sum, in its order)
+template <int HD>
+__device__ __forceinline__ void tl_attn_kb_rows(const TlAttnBwdArgs& a, int s, int h, int row0, float* lse_s, float* delta_s, const Thr& t) {
+    if (t.tid < TL_KB) {
+        const int r = row0 + t.tid;
+        const float* og = frow(a.o, s, r) + h * HD;
+        const float* dg = frow(a.dO, s, r) + h * HD;
+        float p = 0.f;
+#pragma unroll
+        for (int c = 0; c < HD; c += 4) {
+            const float4 ov = ld4(og + c), dv = ld4(dg + c);
+            p = fmaf(ov.x, dv.x, p); p = fmaf(ov.y, dv.y, p); p = fmaf(ov.z, dv.z, p); p = fmaf(ov.w, dv.w, p);
+        }
+        delta_s[t.tid] = p;
+        lse_s[t.tid] = a.lse.base[(size_t)s * a.lse.stride + (size_t)h * a.lpb + r];
+    }
+}
+
+// Backward, dk | dv: grid (S, H, LPB / 64), key block z (the long ones first); k | v of the block in registers, q | dO of the query
+// blocks at and above it staged in turn.  attention_backward_group_mfma's pass 2; nothing is accumulated across workgroups.
+template <int HD, bool DROP>
+__global__ __launch_bounds__(256) void tl_attn_kb_dkv_kernel(TlAttnBwdArgs a) {
+    constexpr int LDK = 2 * HD + 4, KS = HD / 4, CT = (HD + 15) / 16;
+    constexpr float LOG2E = 1.4426950408889634f;
+    __shared__ __attribute__((aligned(16))) float QD[TL_KB * LDK];     // [64][q | dO] of this head
+    __shared__ __attribute__((aligned(16))) float lse_s[TL_KB];
+    __shared__ __attribute__((aligned(16))) float delta_s[TL_KB];
+    const Thr t = make_thr();
+    const int s = (int)blockIdx.x, h = (int)blockIdx.y, kb = (int)blockIdx.z;
+    const int tj = kb * 4 + t.wave, srow = tj * 16 + t.i;
+    const int ti_hi = (a.n - 1) / 16;                                  // last query tile with live rows
+    float* kout = frow(a.dqkv, s, srow) + a.D + h * HD;
+    float* vout = kout + a.D;
+    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (kb * 4 > ti_hi) {                                              // keys no live query sees: dk = dv = 0
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct)
+            if (ct * 16 + t.kq * 4 < HD) { st4(kout + ct * 16 + t.kq * 4, z4); st4(vout + ct * 16 + t.kq * 4, z4); }
+        return;
+    }
+    const bool live_tile = tj <= ti_hi;
+    const float scale = 1.0f / sqrtf(a.hd_eff), scale2 = scale * LOG2E;
+    float kf[KS], vf[KS];
+    {
+        const float* kp = frow(a.qkv, s, srow) + a.D + h * HD + t.kq * KS;
+#pragma unroll
+        for (int c = 0; c < KS; ++c) {
+            kf[c] = live_tile ? kp[c] * scale2 : 0.f;
+            vf[c] = live_tile ? kp[a.D + c] : 0.f;
+        }
+    }
+    f32x4 acck[CT][2], accv[CT][2];
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) { acck[ct][0] = zero4(); acck[ct][1] = zero4(); accv[ct][0] = zero4(); accv[ct][1] = zero4(); }
+    Drop dr = drop_off();
+    if constexpr (DROP) dr = tl_drop(a.drop, s);
+    for (int qb = kb; qb * 4 <= ti_hi; ++qb) {
+        if (qb > kb) __syncthreads();
+        for (int idx = t.tid; idx < TL_KB * 2 * (HD / 4); idx += 256) {
+            const int r = idx / (2 * (HD / 4)), rem = idx - r * (2 * (HD / 4));
+            const int which = rem / (HD / 4), c = (rem - which * (HD / 4)) * 4;
+            const float* p = which == 0 ? frow(a.qkv, s, qb * TL_KB + r) + h * HD + c : frow(a.dO, s, qb * TL_KB + r) + h * HD + c;
+            st4(QD + r * LDK + which * HD + c, ld4(p));
+        }
+        tl_attn_kb_rows<HD>(a, s, h, qb * TL_KB, lse_s, delta_s, t);
+        __syncthreads();
+        if (!live_tile) continue;
+#pragma unroll 1
+        for (int u = 0; u < 4; ++u) {
+            const int ti = qb * 4 + u;
+            if (ti < tj) continue;
+            if (ti > ti_hi) break;
+            const int t0 = ti * 16;
+            const float* qp = QD + (u * 16 + t.i) * LDK + t.kq * KS;
+            const float* dop = qp + HD;
+            f32x4 st = zero4(), dp = zero4();
+#pragma unroll
+            for (int c = 0; c < KS; ++c) {
+                st = mfma16(qp[c], kf[c], st);
+                dp = mfma16(dop[c], vf[c], dp);
+            }
+            // st[r] = S[t0 + kq*4 + r][srow]
+            const float4 l4 = ld4(lse_s + u * 16 + t.kq * 4), d4 = ld4(delta_s + u * 16 + t.kq * 4);
+            const float lse4[4] = {l4.x, l4.y, l4.z, l4.w}, del4[4] = {d4.x, d4.y, d4.z, d4.w};
+            float p[4], ds[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int tr = t0 + t.kq * 4 + r;
+                p[r] = DTQN_EXP2(st[r] - lse4[r] * LOG2E);
+                if (srow > tr || tr >= a.n) p[r] = 0.f;
+                float dpm = dp[r];
+                if (dr.thresh != 0u) {
+                    const bool keep = drop_keep(dr, DROP_ATTN, a.layer, drop_attn_idx(h, tr, srow));
+                    dpm = keep ? dp[r] * dr.scale : 0.f;
+                    ds[r] = p[r] * (dpm - del4[r]);
+                    p[r] = keep ? p[r] * dr.scale : 0.f;               // dV takes the dropped probabilities
+                } else {
+                    ds[r] = p[r] * (dpm - del4[r]);
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float* qrow = QD + (u * 16 + t.kq * 4 + r) * LDK;
+                const float* dorow = qrow + HD;
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct) {
+                    const int c = ct * 16 + t.i;
+                    const int cc = c < HD ? c : 0;
+                    acck[ct][r & 1] = mfma16(qrow[cc], ds[r], acck[ct][r & 1]);
+                    accv[ct][r & 1] = mfma16(dorow[cc], p[r], accv[ct][r & 1]);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) {
+        const int c = ct * 16 + t.kq * 4;
+        if (c < HD) {
+            st4(kout + c, make_float4((acck[ct][0][0] + acck[ct][1][0]) * scale, (acck[ct][0][1] + acck[ct][1][1]) * scale,
+                                      (acck[ct][0][2] + acck[ct][1][2]) * scale, (acck[ct][0][3] + acck[ct][1][3]) * scale));
+            st4(vout + c, make_float4(accv[ct][0][0] + accv[ct][1][0], accv[ct][0][1] + accv[ct][1][1],
+                                      accv[ct][0][2] + accv[ct][1][2], accv[ct][0][3] + accv[ct][1][3]));
+        }
+    }
+}
+
+// Backward, dq: grid (S, H, LPB / 64), query block nqb - 1 - z; q | dO of the block in registers, k | v of the key blocks at and below it
+// staged in turn.  attention_backward_group_mfma's pass 1.
+template <int HD, bool DROP>
+__global__ __launch_bounds__(256) void tl_attn_kb_dq_kernel(TlAttnBwdArgs a) {
+    constexpr int LDK = 2 * HD + 4, KS = HD / 4, CT = (HD + 15) / 16;
+    constexpr float LOG2E = 1.4426950408889634f;
+    __shared__ __attribute__((aligned(16))) float KV[TL_KB * LDK];     // [64][k | v] of this head
+    __shared__ __attribute__((aligned(16))) float lse_s[TL_KB];
+    __shared__ __attribute__((aligned(16))) float delta_s[TL_KB];
+    const Thr t = make_thr();
+    const int s = (int)blockIdx.x, h = (int)blockIdx.y, qb = a.lpb / TL_KB - 1 - (int)blockIdx.z;
+    const int ti = qb * 4 + t.wave, trow = ti * 16 + t.i;
+    const int last_tile = (a.n - 1) / 16;
+    float* dqp = frow(a.dqkv, s, trow) + h * HD;
+    if (qb * 4 > last_tile) {                                          // pad rows: dq = 0
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct)
+            if (ct * 16 + t.kq * 4 < HD) st4(dqp + ct * 16 + t.kq * 4, make_float4(0.f, 0.f, 0.f, 0.f));
+        return;
+    }
+    const bool live_tile = ti <= last_tile;
+    const float scale = 1.0f / sqrtf(a.hd_eff), scale2 = scale * LOG2E;
+    tl_attn_kb_rows<HD>(a, s, h, qb * TL_KB, lse_s, delta_s, t);
+    float qf[KS], dof[KS];
+    {
+        const float* qp = frow(a.qkv, s, trow) + h * HD + t.kq * KS;
+        const float* dp = frow(a.dO, s, trow) + h * HD + t.kq * KS;
+#pragma unroll
+        for (int c = 0; c < KS; ++c) {
+            qf[c] = live_tile ? qp[c] * scale2 : 0.f;
+            dof[c] = live_tile ? dp[c] : 0.f;
+        }
+    }
+    f32x4 acc[CT][2];
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) { acc[ct][0] = zero4(); acc[ct][1] = zero4(); }
+    Drop dr = drop_off();
+    if constexpr (DROP) dr = tl_drop(a.drop, s);
+    float lse2 = 0.f, delta = 0.f;
+    for (int kb = 0; kb <= qb; ++kb) {
+        if (kb > 0) __syncthreads();
+        for (int idx = t.tid; idx < TL_KB * 2 * (HD / 4); idx += 256) {
+            const int r = idx / (2 * (HD / 4)), rem = idx - r * (2 * (HD / 4));
+            const int which = rem / (HD / 4), c = (rem - which * (HD / 4)) * 4;
+            st4(KV + r * LDK + which * HD + c, ld4(frow(a.qkv, s, kb * TL_KB + r) + (1 + which) * a.D + h * HD + c));
+        }
+        __syncthreads();
+        if (!live_tile) continue;
+        if (kb == 0) { lse2 = lse_s[t.wave * 16 + t.i] * LOG2E; delta = delta_s[t.wave * 16 + t.i]; }
+#pragma unroll 1
+        for (int u = 0; u < 4; ++u) {
+            const int tj = kb * 4 + u;
+            if (tj > ti) break;
+            const int s0 = tj * 16;
+            const float* kp = KV + (u * 16 + t.i) * LDK + t.kq * KS;
+            const float* vp = kp + HD;
+            f32x4 st = zero4(), dp = zero4();
+#pragma unroll
+            for (int c = 0; c < KS; ++c) {
+                st = mfma16(kp[c], qf[c], st);
+                dp = mfma16(vp[c], dof[c], dp);
+            }
+            float ds[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                float p = DTQN_EXP2(st[r] - lse2);
+                if (s0 + t.kq * 4 + r > trow || trow >= a.n) p = 0.f;     // masked keys; pad query rows (see attention_backward_group_mfma)
+                const float dpm = dr.thresh == 0u ? dp[r] : (drop_keep(dr, DROP_ATTN, a.layer, drop_attn_idx(h, trow, s0 + t.kq * 4 + r)) ? dp[r] * dr.scale : 0.f);
+                ds[r] = p * (dpm - delta);
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float* krow = KV + (u * 16 + t.kq * 4 + r) * LDK;
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct) {
+                    const int c = ct * 16 + t.i;
+                    acc[ct][r & 1] = mfma16(krow[c < HD ? c : 0], ds[r], acc[ct][r & 1]);
+                }
+            }
+        }
+    }
+    const float f = live_tile && trow < a.n ? scale : 0.f;
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) {
+        const int c = ct * 16 + t.kq * 4;
+        if (c < HD)
+            st4(dqp + c, make_float4((acc[ct][0][0] + acc[ct][1][0]) * f, (acc[ct][0][1] + acc[ct][1][1]) * f,
+                                     (acc[ct][0][2] + acc[ct][1][2]) * f, (acc[ct][0][3] + acc[ct][1][3]) * f));
+    }
+}
+
 // ---- LayerNorm over 64-row blocks -----------------------------------------------------------------------------------
 struct TlLnArgs {
     Fld src, dst, st;                  // st: (mean, rstd) per row, base may be null
@@ -2822,8 +3109,26 @@ static int launch_ln_bwd(const TlLnBwdArgs& a, int S, hipStream_t stream) {
 }
 // head_dim instantiations of the attention kernels (dtqn_net_init admits exactly these on the row-block path)
 #define TL_ATTN_HEAD_DIMS(X) X(4) X(8) X(16) X(32) X(64) X(128)
+// The key-blocked kernels (tl_attn_kb_*) take over exactly where the whole-head tile does not fit LDS (dtqn_attn_whole_tile, the test
+// dtqn_net_init admits shapes by); DTQN_ATTN_KBLOCK=1 (A/B and tests, read per launch) forces them on any row-block shape.
+static inline bool tl_attn_kblock(int lpb, int HD) {
+    const char* e = getenv("DTQN_ATTN_KBLOCK");
+    return (e != nullptr && e[0] == '1') || !dtqn_attn_whole_tile(lpb, HD);
+}
 static int launch_attn(const TlAttnArgs& a, int S, int H, int HD, hipStream_t stream) {
-    const size_t lds = (size_t)a.lpb * (3 * HD + 4) * sizeof(float);
+    const size_t lds = dtqn_attn_tile_lds(a.lpb, HD, 0);
+    if (tl_attn_kblock(a.lpb, HD)) {
+        const dim3 grid(S, H, a.lpb / TL_KB);
+#define TL_ATTN_CASE(hd)                                                                                             \
+        if (HD == hd) {                                                                                              \
+            if (a.drop.thresh != 0u) TL_LAUNCH((tl_attn_kb_kernel<hd, true>), grid, dim3(256), 0, stream, a);        \
+            else TL_LAUNCH((tl_attn_kb_kernel<hd, false>), grid, dim3(256), 0, stream, a);                           \
+            return DTQN_OK;                                                                                          \
+        }
+        TL_ATTN_HEAD_DIMS(TL_ATTN_CASE)
+#undef TL_ATTN_CASE
+        return DTQN_ERR_CONFIG;
+    }
 #define TL_ATTN_CASE(hd)                                                                                             \
     if (HD == hd) {                                                                                                  \
         if (a.drop.thresh != 0u) TL_LAUNCH((tl_attn_kernel<hd, true>), dim3(S, H), dim3(256), lds, stream, a);       \
@@ -2835,7 +3140,24 @@ static int launch_attn(const TlAttnArgs& a, int S, int H, int HD, hipStream_t st
     return DTQN_ERR_CONFIG;
 }
 static int launch_attn_bwd(const TlAttnBwdArgs& a, int S, int H, int HD, hipStream_t stream) {
-    const size_t lds = ((size_t)a.lpb * (4 * HD + 4) + 2 * (size_t)a.lpb) * sizeof(float);
+    const size_t lds = dtqn_attn_tile_lds(a.lpb, HD, 1);
+    if (tl_attn_kblock(a.lpb, HD)) {        // dk | dv, then dq: both read only the forward's records and dO, and write disjoint columns
+        const dim3 grid(S, H, a.lpb / TL_KB);
+#define TL_ATTN_CASE(hd)                                                                                             \
+        if (HD == hd) {                                                                                              \
+            if (a.drop.thresh != 0u) {                                                                               \
+                TL_LAUNCH((tl_attn_kb_dkv_kernel<hd, true>), grid, dim3(256), 0, stream, a);                         \
+                TL_LAUNCH((tl_attn_kb_dq_kernel<hd, true>), grid, dim3(256), 0, stream, a);                          \
+            } else {                                                                                                 \
+                TL_LAUNCH((tl_attn_kb_dkv_kernel<hd, false>), grid, dim3(256), 0, stream, a);                        \
+                TL_LAUNCH((tl_attn_kb_dq_kernel<hd, false>), grid, dim3(256), 0, stream, a);                         \
+            }                                                                                                        \
+            return DTQN_OK;                                                                                          \
+        }
+        TL_ATTN_HEAD_DIMS(TL_ATTN_CASE)
+#undef TL_ATTN_CASE
+        return DTQN_ERR_CONFIG;
+    }
 #define TL_ATTN_CASE(hd)                                                                                             \
     if (HD == hd) {                                                                                                  \
         if (a.drop.thresh != 0u) TL_LAUNCH((tl_attn_bwd_kernel<hd, true>), dim3(S, H), dim3(256), lds, stream, a);   \
