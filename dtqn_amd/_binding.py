@@ -132,6 +132,9 @@ def load_library(path: str) -> ctypes.CDLL:
         "dtqn_img_backward": [P(DtqnNet), vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp],
         "dtqn_img_td_lists": [P(DtqnNet), P(DtqnReplay), P(DtqnTd), vp, vp, vp, vp, vp, vp, vp],
         "dtqn_forward_tiled_pre": [P(DtqnNet), vp, vp, vp, i32, i32, vp, vp, i32, u32, u32, vp],
+        "dtqn_grad_workspace_floats": [P(DtqnNet), i32, i32],
+        "dtqn_forward_train": [P(DtqnNet), vp, vp, vp, vp, vp, i32, i32, vp, vp, vp],
+        "dtqn_backward_dq": [P(DtqnNet), vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp],
         "dtqn_xch_publish": [vp, i32, vp],
         "dtqn_td_xreduce": [P(DtqnNet), P(DtqnTd), vp, vp, i32, i32, vp, vp, vp, vp],
         "dtqn_td_update": [P(DtqnNet), P(DtqnReplay), P(DtqnTd), vp],
@@ -147,7 +150,8 @@ def load_library(path: str) -> ctypes.CDLL:
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = ctypes.c_char_p if name == "dtqn_build_info" else (
-            ctypes.c_longlong if name in ("dtqn_img_act_floats", "dtqn_img_gact_floats", "dtqn_img_wpart_floats") else ctypes.c_int)
+            ctypes.c_longlong if name in ("dtqn_img_act_floats", "dtqn_img_gact_floats", "dtqn_img_wpart_floats",
+                                                    "dtqn_grad_workspace_floats") else ctypes.c_int)
     assert set(protos) == set(FUNCTIONS), sorted(set(protos) ^ set(FUNCTIONS))
     if lib.dtqn_abi_version() != DEFINES["DTQN_ABI_VERSION"]:
         raise OSError(f"{path}: ABI version {lib.dtqn_abi_version()} != header {DEFINES['DTQN_ABI_VERSION']}")

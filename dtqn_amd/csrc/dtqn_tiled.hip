@@ -2634,10 +2634,11 @@ struct TlEmbedBwdArgs {
     const float* obs;
     const uint8_t* actions;
     long long obs_ep_stride, act_ep_stride;
-    const int32_t* ep_idx;
-    const int32_t* start;
-    // bag entries (second pass over the same partials): gradient at grd + dx_off instead of go_dx0, `rows` live rows read from
-    // source sequence b of (obs, actions) directly, action embedding not rolled, partials ADDED to the context's
+    const int32_t* ep_idx;             // replay windows (TD): sequence b reads episode ep_idx[b] from row start[b]; nullptr: source
+    const int32_t* start;              //   sequence b of (obs, actions) directly from row 0 (caller arrays, dtqn_backward_dq)
+    // rows: live rows of every sequence (ctx_len in a TD update).  Bag entries (second pass over the same partials): gradient at
+    // grd + dx_off instead of go_dx0, `rows` live rows read from source sequence b directly, action embedding not rolled, partials
+    // ADDED to the context's
     int bag, dx_off, rows;
 };
 // One workgroup per (sequence, 64-row block); its partials go to the small-partial record of that row block.
@@ -2666,11 +2667,12 @@ __global__ __launch_bounds__(TNT) void tl_embed_bwd_kernel(TlEmbedBwdArgs a) {
     const Thr t = make_thr();
     const int tid = t.tid;
     const int rpb = net.lp / TROWS, b = (int)blockIdx.x / rpb, rb = (int)blockIdx.x % rpb, row0 = rb * TROWS;
-    const int D = net.d_model, L = a.bag ? a.rows : net.ctx_len, A = net.num_actions, adim = net.action_dim;
+    const int D = net.d_model, L = a.rows, A = net.num_actions, adim = net.action_dim;
     if (a.bag && row0 >= L) return;                                    // bag pass: nothing of the bag in this row block
     const float* DX = a.grd + (size_t)b * net.grd_stride + (a.bag ? a.dx_off : net.go_dx0) + (size_t)row0 * D;
     float* srec = a.small + ((size_t)b * rpb + rb) * net.sp_stride;
-    const int ep = a.bag ? b : a.ep_idx[b], st0 = a.bag ? 0 : a.start[b];
+    const bool direct = a.bag || a.ep_idx == nullptr;
+    const int ep = direct ? b : a.ep_idx[b], st0 = direct ? 0 : a.start[b];
     const float* obs_rows = a.obs + (size_t)ep * a.obs_ep_stride + (size_t)(st0 + row0) * net.obs_dim;
     const uint8_t* act_rows = a.actions + (size_t)ep * a.act_ep_stride + st0;
     const int nrows = L - row0 < TROWS ? L - row0 : TROWS;             // live rows of this block
@@ -2772,6 +2774,45 @@ __global__ __launch_bounds__(TNT) void tl_embed_bwd_kernel(TlEmbedBwdArgs a) {
             srec[net.so_act + idx] = a.bag ? srec[net.so_act + idx] + g : g;
         }
     }
+}
+
+// ---- caller-supplied dL/dQ (dtqn_backward_dq): the loss of tl_loss_kernel is the caller's --------------------------------------
+// dq [B][n][A] -> the go_dq record [LP][AP] of every sequence, rows >= n and action columns >= A zero.  One workgroup per sequence.
+struct TlDqInArgs {
+    const float* dq;
+    float* grd;
+    long long grd_stride;
+    int go_dq, n, A, LP, AP;
+};
+__global__ __launch_bounds__(256) void tl_dq_in_kernel(TlDqInArgs a) {
+    const int b = (int)blockIdx.x;
+    float* out = a.grd + (size_t)b * a.grd_stride + a.go_dq;
+    const float* in = a.dq + (size_t)b * a.n * a.A;
+    for (int idx = (int)threadIdx.x; idx < a.LP * a.AP; idx += 256) {
+        const int r = idx / a.AP, c = idx - r * a.AP;
+        out[idx] = (r < a.n && c < a.A) ? in[(size_t)r * a.A + c] : 0.f;
+    }
+}
+
+// ---- observation gradient (continuous observations): dobs[b][t][:] = dx0[b][t][a:] W_obs ([D - a][O]) ---------------------------
+// One thread per output element, the contraction in a fixed order: deterministic, no atomics, no scratch.  O is any width >= 1 (not
+// the 64-aligned launch_dx): the product is tiny next to the chain, B n O (D - a) multiply-adds.
+struct TlDobsArgs {
+    const float* grd;
+    const float* W;                    // theta + off_obs_w: [D - a][O]
+    float* dobs;                       // [B][n][O]
+    long long grd_stride;
+    int go_dx0, D, adim, O, n, total;  // total = B n O
+};
+__global__ __launch_bounds__(256) void tl_dobs_kernel(TlDobsArgs a) {
+    const int idx = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (idx >= a.total) return;
+    const int o = idx % a.O, bt = idx / a.O, b = bt / a.n, t = bt - b * a.n;
+    const float* dx = a.grd + (size_t)b * a.grd_stride + a.go_dx0 + (size_t)t * a.D + a.adim;
+    const float* w = a.W + o;
+    float g = 0.f;
+    for (int d = 0; d < a.D - a.adim; ++d) g = fmaf(dx[d], w[(size_t)d * a.O], g);
+    a.dobs[idx] = g;
 }
 
 // ---- bag attention (dtqn.py:211-213): nn.MultiheadAttention(query = working memory, key = value = bag embeddings), no mask ----
@@ -3518,24 +3559,35 @@ static int forward_records(const DtqnNet& net, const float* theta_a, const float
     return DTQN_OK;
 }
 
+// What the backward reads besides the records: the B sequences' inputs (replay windows of a TD update, or the caller's [B][n] arrays),
+// their live rows, the forward's dropout, and where dL/dQ comes from.
+struct BwdIn {
+    const DtqnReplay* rp;              // TD update: the double-DQN loss (tl_loss_kernel) writes dL/dQ from the replay; nullptr: dL/dQ is
+                                       // already in the go_dq records (dtqn_backward_dq, tl_dq_in_kernel)
+    EmbedSrc src;                      // observations / actions (+ bag) of sequence b: ep_idx / start windows, or sequence b directly
+    int n;                             // live rows: rows n .. lp - 1 are pad rows of the attention backward (no gradient flows into them)
+    TlDrop drop;                       // the keep masks of the forward the records came from
+};
+
 // Data-gradient chain of the B TRAIN sequences (records [0, B) of td->act), residual gate; post-LN (transformer.py:63-78)
 // or identity-reordered (transformer.py:86-101) layers.
 // The gradient of the residual stream lives in grd.go_dx0 throughout (it IS dL/dx0 at the end).
 template <int D>
-static int backward_records(const DtqnNet& net, const DtqnReplay& rp, const DtqnTd& td, hipStream_t stream) {
+static int backward_records(const DtqnNet& net, const BwdIn& in, const DtqnTd& td, hipStream_t stream) {
     constexpr int KC = D < 128 ? D : 128;
-    const int lpb = net.lp, H = net.num_heads, HD = net.head_dim, rpb = lpb / TROWS, B = td.batch, L = net.ctx_len;
+    const int lpb = net.lp, H = net.num_heads, HD = net.head_dim, rpb = lpb / TROWS, B = td.batch, L = in.n;
     const float* theta = td.theta_pol;
     float* act = td.act;
     float* grd = td.grd;
     int rc;
     auto FA = [&](int off, int ld) { return fld(act, net.act_stride, off, ld); };
     auto FG = [&](int off, int ld) { return fld(grd, net.grd_stride, off, ld); };
-    const long long obs_ep_stride = (long long)(rp.max_steps + 1) * rp.obs_dim, act_ep_stride = rp.max_steps + 1;
     // fragment-major B copies of the policy weights (dtqn_wpack.hpp), written by this update's forward
     const float* pk = td.wpack_tgt != nullptr ? td.wpack_pol : nullptr;
     const WPackPlan wplan = pk != nullptr ? wpack_plan(net) : WPackPlan{};
-    {
+    if (in.rp != nullptr) {
+        const DtqnReplay& rp = *in.rp;
+        const long long act_ep_stride = rp.max_steps + 1;
         TlLossArgs a;
         a.net = net; a.q3 = td.q3; a.grd = grd; a.stats_partial = td.stats_partial;
         a.actions = rp.actions; a.rewards = rp.rewards; a.dones = rp.dones;
@@ -3574,8 +3626,7 @@ static int backward_records(const DtqnNet& net, const DtqnReplay& rp, const Dtqn
         return DTQN_OK;
     };
     const bool ident = net.identity != 0, gru = net.gate == DTQN_GATE_GRU;
-    // the training forward's dropout (pass 0 of the TD update), recomputed: step = step_counter[1], not yet advanced
-    const TlDrop drop = tl_drop_make(net, td.dropout_seed, 0u, td.step_counter, B, 0x1);
+    const TlDrop drop = in.drop;
     auto drop_rows = [&](Fld x, int site, int layer) -> int {
         TlDropRowsArgs a;
         a.x = x; a.D = D; a.rpb = rpb; a.site = site; a.layer = layer; a.drop = drop;
@@ -3609,7 +3660,7 @@ static int backward_records(const DtqnNet& net, const DtqnReplay& rp, const Dtqn
     if (net.bag_size > 0) {
         // d xcat = dhh W_1 ([D][2D]); its left half is dL/d(working memory) so far, its right half dL/d(persistent memory)
         const int bag = net.bag_size;
-        if (!td.bag_obs || (net.action_dim > 0 && !td.bag_actions)) return DTQN_ERR_ARG;
+        if (!in.src.bag_obs || (net.action_dim > 0 && !in.src.bag_actions)) return DTQN_ERR_ARG;
         if ((rc = dx(FG(net.go_dhh, D), D, net.off_head1_w, 2 * D, FG(net.go_dcat, 2 * D), 0, nofld())) != DTQN_OK) return rc;
         {
             TlCopyArgs c;
@@ -3727,15 +3778,15 @@ static int backward_records(const DtqnNet& net, const DtqnReplay& rp, const Dtqn
     if (net.discrete || net.action_dim > 0) {
         TlEmbedBwdArgs a;
         a.net = net; a.theta = theta; a.grd = grd; a.small = td.small;
-        a.obs = rp.obs; a.actions = rp.actions; a.obs_ep_stride = obs_ep_stride; a.act_ep_stride = act_ep_stride;
-        a.ep_idx = td.ep_idx; a.start = td.start;
+        a.obs = in.src.obs; a.actions = in.src.actions; a.obs_ep_stride = in.src.obs_ep_stride; a.act_ep_stride = in.src.act_ep_stride;
+        a.ep_idx = in.src.ep_idx; a.start = in.src.start;
         const size_t lds = tl_embed_bwd_lds(net);
         // (KE <= 256: at most 4 x 16 column tiles x 4 row tiles = the 4 items a wave keeps accumulators for)
         if (lds > 150 * 1024 || (net.discrete && net.ke > 128)) return DTQN_ERR_CONFIG;
-        a.bag = 0; a.dx_off = 0; a.rows = 0;
+        a.bag = 0; a.dx_off = 0; a.rows = L;
         TL_LAUNCH(tl_embed_bwd_kernel, dim3(B * rpb), dim3(TNT), lds, stream, a);
         if (net.bag_size > 0) {          // the bag entries went through the same tables: their partials are added
-            a.obs = td.bag_obs; a.actions = td.bag_actions;
+            a.obs = in.src.bag_obs; a.actions = in.src.bag_actions; a.ep_idx = nullptr; a.start = nullptr;
             a.obs_ep_stride = (long long)net.bag_size * net.obs_dim; a.act_ep_stride = net.bag_size;
             a.bag = 1; a.dx_off = net.go_bag_de; a.rows = net.bag_size;
             TL_LAUNCH(tl_embed_bwd_kernel, dim3(B * rpb), dim3(TNT), lds, stream, a);
@@ -3789,10 +3840,19 @@ int tiled_td_forward_part(const DtqnNet* net, const DtqnReplay* rp, const DtqnTd
 }
 
 int tiled_td_backward(const DtqnNet* net, const DtqnReplay* rp, const DtqnTd* td, hipStream_t stream) {
+    BwdIn in;
+    in.rp = rp;
+    in.src.obs = rp->obs; in.src.actions = rp->actions;
+    in.src.obs_ep_stride = (long long)(rp->max_steps + 1) * rp->obs_dim; in.src.act_ep_stride = rp->max_steps + 1;
+    in.src.ep_idx = td->ep_idx; in.src.start = td->start; in.src.batch = td->batch;
+    in.src.bag_obs = td->bag_obs; in.src.bag_actions = td->bag_actions; in.src.bag_batch = td->batch;
+    in.n = net->ctx_len;
+    // the training forward's dropout (pass 0 of the TD update), recomputed: step = step_counter[1], not yet advanced
+    in.drop = tl_drop_make(*net, td->dropout_seed, 0u, td->step_counter, td->batch, 0x1);
     switch (net->d_model) {
-        case 64: return backward_records<64>(*net, *rp, *td, stream);
-        case 128: return backward_records<128>(*net, *rp, *td, stream);
-        case 256: return backward_records<256>(*net, *rp, *td, stream);
+        case 64: return backward_records<64>(*net, in, *td, stream);
+        case 128: return backward_records<128>(*net, in, *td, stream);
+        case 256: return backward_records<256>(*net, in, *td, stream);
         default: return DTQN_ERR_CONFIG;
     }
 }
@@ -3875,4 +3935,111 @@ extern "C" int dtqn_forward_bag(const DtqnNet* net, const float* theta, const fl
     if (!net || net->bag_size < 1) return DTQN_ERR_ARG;
     return forward_tiled_impl(net, theta, obs, actions, bag_obs, bag_actions, batch, n, n, q_out, workspace, stream, train_mode, dropout_seed,
                               dropout_step);
+}
+
+// ---- differentiable forward (torch autograd, dtqn_amd/networks/dtqn.py): the forward of the caller's [B][n] inputs keeps the activation
+// records of all B sequences, the backward runs the TD update's chain and weight-gradient kernels from a caller-supplied dL/dQ.
+// Workspace (floats): act [B][act_stride] | grd [B][grd_stride] | small [B sp_parts][sp_stride] | gsplit [n_split][n_trainable] |
+// norm_partial | step_counter (4 ints).  The forward writes act; everything behind it is the backward's scratch.
+namespace {
+struct GradWs {
+    long long grd, small, gsplit, norm, steps, total;
+    int n_split, n_norm_blocks;
+};
+GradWs grad_ws(const DtqnNet& net, int batch) {
+    GradWs w;
+    w.n_split = dtqn_td_wgrad_is_direct(&net, batch) ? 1 : dtqn_td_wgrad_splits(&net, batch);
+    w.n_norm_blocks = (net.n_trainable + 1023) / 1024;
+    const int np = dtqn_td_norm_partials(&net), n_norm = np > w.n_norm_blocks ? np : w.n_norm_blocks;
+    auto up4 = [](long long v) { return (v + 3) & ~3LL; };
+    w.grd = up4((long long)batch * net.act_stride);
+    w.small = w.grd + up4((long long)batch * net.grd_stride);
+    w.gsplit = w.small + up4((long long)batch * net.sp_parts * net.sp_stride);
+    w.norm = w.gsplit + up4((long long)w.n_split * net.n_trainable);
+    w.steps = w.norm + up4(n_norm);
+    w.total = w.steps + 4;
+    return w;
+}
+bool grad_net_ok(const DtqnNet* net) { return net->tiled && net->img_c == 0; }
+}  // namespace
+
+extern "C" long long dtqn_grad_workspace_floats(const DtqnNet* net, int batch, int n) {
+    if (!net || batch < 1 || n < 1 || n > net->ctx_len || !grad_net_ok(net)) return 0;
+    return grad_ws(*net, batch).total;
+}
+
+extern "C" int dtqn_forward_train(const DtqnNet* net, const float* theta, const float* obs, const uint8_t* actions, const float* bag_obs,
+                                  const uint8_t* bag_actions, int batch, int n, float* q_out, float* workspace, void* stream) {
+    if (!net || !theta || !obs || !q_out || !workspace || batch < 1) return DTQN_ERR_ARG;
+    if (!grad_net_ok(net)) return DTQN_ERR_CONFIG;          // whole-sequence nets: their dtqn_net_tiled_twin; image nets: not covered
+    if (n < 1 || n > net->ctx_len) return DTQN_ERR_ARG;     // dtqn.py:170-173
+    if (net->action_dim > 0 && !actions) return DTQN_ERR_ARG;
+    if (net->bag_size > 0 && (!bag_obs || (net->action_dim > 0 && !bag_actions))) return DTQN_ERR_ARG;
+    EmbedSrc src;
+    src.obs = obs; src.actions = actions;
+    src.obs_ep_stride = (long long)n * net->obs_dim; src.act_ep_stride = n;
+    src.ep_idx = nullptr; src.start = nullptr; src.batch = batch;         // seq0 = 0: every sequence's records are kept
+    src.bag_obs = bag_obs; src.bag_actions = bag_actions; src.bag_batch = batch;
+    const long long qs = (long long)n * net->num_actions;
+    hipStream_t s = (hipStream_t)stream;
+    // no dropout: the function the no-grad forward computes (its default), with the records of a training forward
+    switch (net->d_model) {
+        case 64: return forward_records<64>(*net, theta, theta, batch, src, batch, n, workspace, true, q_out, qs, net->num_actions, s, tl_drop_none());
+        case 128: return forward_records<128>(*net, theta, theta, batch, src, batch, n, workspace, true, q_out, qs, net->num_actions, s, tl_drop_none());
+        case 256: return forward_records<256>(*net, theta, theta, batch, src, batch, n, workspace, true, q_out, qs, net->num_actions, s, tl_drop_none());
+        default: return DTQN_ERR_CONFIG;
+    }
+}
+
+extern "C" int dtqn_backward_dq(const DtqnNet* net, const float* theta, const float* obs, const uint8_t* actions, const float* bag_obs,
+                                const uint8_t* bag_actions, int batch, int n, const float* dq, float* workspace, float* grad, float* dobs,
+                                void* stream) {
+    if (!net || !theta || !obs || !dq || !workspace || !grad || batch < 1) return DTQN_ERR_ARG;
+    if (!grad_net_ok(net)) return DTQN_ERR_CONFIG;
+    if (n < 1 || n > net->ctx_len) return DTQN_ERR_ARG;
+    if (net->action_dim > 0 && !actions) return DTQN_ERR_ARG;
+    if (net->bag_size > 0 && (!bag_obs || (net->action_dim > 0 && !bag_actions))) return DTQN_ERR_ARG;
+    if (dobs != nullptr && net->discrete) return DTQN_ERR_ARG;     // tokens have no gradient
+    hipStream_t s = (hipStream_t)stream;
+    const GradWs w = grad_ws(*net, batch);
+    DtqnTd td = {};
+    td.theta_pol = const_cast<float*>(theta);
+    td.grad = grad;
+    td.act = workspace; td.grd = workspace + w.grd; td.small = workspace + w.small; td.gsplit = workspace + w.gsplit;
+    td.norm_partial = workspace + w.norm; td.step_counter = reinterpret_cast<int32_t*>(workspace + w.steps);
+    td.batch = batch; td.history = 1; td.n_split = w.n_split; td.n_norm_blocks = w.n_norm_blocks; td.row_split = 1;
+    {
+        TlDqInArgs a;
+        a.dq = dq; a.grd = td.grd; a.grd_stride = net->grd_stride; a.go_dq = net->go_dq;
+        a.n = n; a.A = net->num_actions; a.LP = net->lp; a.AP = net->ap;
+        TL_LAUNCH(tl_dq_in_kernel, dim3(batch), dim3(256), 0, s, a);
+    }
+    BwdIn in;
+    in.rp = nullptr;
+    in.src.obs = obs; in.src.actions = actions;
+    in.src.obs_ep_stride = (long long)n * net->obs_dim; in.src.act_ep_stride = n;
+    in.src.ep_idx = nullptr; in.src.start = nullptr; in.src.batch = batch;
+    in.src.bag_obs = bag_obs; in.src.bag_actions = bag_actions; in.src.bag_batch = batch;
+    in.n = n;
+    in.drop = tl_drop_none();
+    int rc;
+    switch (net->d_model) {
+        case 64: rc = backward_records<64>(*net, in, td, s); break;
+        case 128: rc = backward_records<128>(*net, in, td, s); break;
+        case 256: rc = backward_records<256>(*net, in, td, s); break;
+        default: return DTQN_ERR_CONFIG;
+    }
+    if (rc != DTQN_OK) return rc;
+    if (dobs != nullptr) {
+        TlDobsArgs a;
+        a.grd = td.grd; a.W = theta + net->off_obs_w; a.dobs = dobs; a.grd_stride = net->grd_stride;
+        a.go_dx0 = net->go_dx0; a.D = net->d_model; a.adim = net->action_dim; a.O = net->obs_dim; a.n = n;
+        const long long total = (long long)batch * n * net->obs_dim;
+        if (total > 0x7fffffffLL) return DTQN_ERR_ARG;
+        a.total = (int)total;
+        TL_LAUNCH(tl_dobs_kernel, dim3((a.total + 255) / 256), dim3(256), 0, s, a);
+    }
+    // weight gradients: the TD update's split-K contraction over act x grd (fixed order), summed into grad by dtqn_td_reduce
+    if ((rc = dtqn_td_wgrad(net, &td, stream)) != DTQN_OK) return rc;
+    return dtqn_td_reduce(net, &td, stream);
 }

@@ -2,13 +2,14 @@
 (dtqn/networks/dtqn.py:16-218), backed by ONE flat fp32 device buffer that the gfx950 kernels
 read directly.
 
-The module is a parameter CONTAINER plus an inference `forward`: every nn.Parameter is a view
+The module is a parameter CONTAINER plus a `forward`: every nn.Parameter is a view
 into `self.flat` (layout: include/dtqn_hip.h, DtqnNet), so `state_dict()` / `load_state_dict()` /
 `parameters()` behave like the reference's -- a policy / target `state_dict` saved by either implementation loads
 in the other (the FULL training checkpoints do not: the reference pickles joblib / torch-optimizer objects, dtqn_amd
 writes plain arrays) --, while the engine
-sees a single contiguous theta.  Training does not go through autograd: DtqnAgent.train() runs the
-fused HIP update on these same buffers.
+sees a single contiguous theta.  DtqnAgent.train() does not go through autograd: it runs the fused HIP
+update on these same buffers.  `DTQN(..., autograd=True)` makes `forward` differentiable for losses written in
+torch (_DtqnForward: the HIP backward of dtqn_backward_dq behind a torch.autograd.Function).
 """
 from __future__ import annotations
 
@@ -18,6 +19,7 @@ from typing import Optional, Union
 import numpy as np
 import torch
 import torch.nn as nn
+from torch.autograd.function import once_differentiable
 
 from .. import _binding as B
 from .. import engine
@@ -52,8 +54,11 @@ class DTQN(nn.Module):
     def __init__(self, obs_dim: int, num_actions: int, embed_per_obs_dim: int, action_dim: int,
                  inner_embed_size: int, num_heads: int, num_layers: int, history_len: int, dropout: float = 0.0,
                  gate: str = "res", identity: bool = False, pos: Union[str, int] = "learned", discrete: bool = False,
-                 vocab_sizes: Optional[Union[np.ndarray, int]] = None, bag_size: int = 0, _test_lib=None, **kwargs):
+                 vocab_sizes: Optional[Union[np.ndarray, int]] = None, bag_size: int = 0, autograd: bool = False, _test_lib=None,
+                 **kwargs):
         super().__init__()
+        # opt-in: callers of the no-grad forward use its output directly (a tensor that requires grad would break .numpy())
+        self._autograd = bool(autograd)
         image = tuple(int(v) for v in obs_dim) if isinstance(obs_dim, (tuple, list, torch.Size)) else None
         if image is not None and len(image) == 2:
             image = (1,) + image                      # representations.py:88-92: H x W means one channel
@@ -97,6 +102,11 @@ class DTQN(nn.Module):
         for l in range(num_layers):
             _attach(self, f"transformer_layers.{l}.attn_mask", nn.Parameter(mask.clone(), requires_grad=False))
         self.reset_parameters()
+
+    def set_autograd(self, flag: bool) -> "DTQN":
+        """Switch the differentiable forward on or off (see forward)."""
+        self._autograd = bool(flag)
+        return self
 
     # ------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -210,12 +220,49 @@ class DTQN(nn.Module):
             raise RuntimeError(f"dtqn_forward_tiled_pre failed with DTQN status {rc}")
         return q
 
-    @torch.no_grad()
     def forward(self, obss: torch.Tensor, actions: Optional[torch.Tensor] = None,
                 bag_obss: Optional[torch.Tensor] = None, bag_actions: Optional[torch.Tensor] = None,
                 _train_dropout: Optional[tuple] = None) -> torch.Tensor:
         """obss [B, seq, obs_dim] (float, or integer tokens for discrete envs), actions [B, seq, 1]
-        -> Q [B, seq, num_actions].  Inference only (no autograd graph)."""
+        -> Q [B, seq, num_actions].  No autograd graph, unless the module was built with autograd=True (or set_autograd(True)),
+        grad mode is on and a trainable parameter or a continuous `obss` requires grad: then Q is the output of a
+        torch.autograd.Function whose backward is the HIP backward (parameters' .grad accumulate as usual; obss.grad for
+        continuous observations).  Both compute the same Q, bit for bit (eval mode: no dropout)."""
+        if self._autograd and torch.is_grad_enabled():
+            if self.image is not None:
+                raise NotImplementedError("DTQN autograd: image observations are not covered by the differentiable forward "
+                                          "(the fused TD update trains image networks)")
+            params = self._grad_params()
+            obs_grad = obss.requires_grad and not self.discrete
+            if obs_grad or any(p.requires_grad for p in params):
+                if _train_dropout is not None and self.dropout_p > 0.0:
+                    raise NotImplementedError("DTQN autograd: the differentiable forward has no train-mode dropout")
+                return _DtqnForward.apply(_GradRunner(self, obss, actions, bag_obss, bag_actions), obss, *params)
+        return self._forward_nograd(obss, actions, bag_obss, bag_actions, _train_dropout)
+
+    def _grad_params(self, with_offsets: bool = False):
+        """Every trainable Parameter once (the shared GRU gate is one Parameter under several keys), in buffer order."""
+        views = sorted((off, p) for (p, off, shape) in self._views.values() if off < self.net.n_trainable)
+        return [(p, off) for off, p in views] if with_offsets else [p for off, p in views]
+
+    def _grad_net(self):
+        """The network the differentiable forward runs on: the net itself (row-block) or its row-block twin (whole-sequence
+        shapes; same theta layout)."""
+        if self.net.tiled:
+            return self.net
+        twin = getattr(self, "_twin", None)
+        if twin is None:
+            twin = B.DtqnNet()
+            if (self._lib.dtqn_net_tiled_twin(ctypes.byref(self.net), ctypes.byref(twin)) != 0 or twin.n_theta != self.net.n_theta
+                    or twin.n_trainable != self.net.n_trainable or B.param_table(twin) != B.param_table(self.net)):
+                raise RuntimeError("DTQN autograd: the row-block twin of this whole-sequence network could not be built")
+            self._twin = twin
+        return twin
+
+    @torch.no_grad()
+    def _forward_nograd(self, obss: torch.Tensor, actions: Optional[torch.Tensor] = None,
+                        bag_obss: Optional[torch.Tensor] = None, bag_actions: Optional[torch.Tensor] = None,
+                        _train_dropout: Optional[tuple] = None) -> torch.Tensor:
         seq = obss.size(1)
         assert seq <= self.history_len, "Cannot forward, history is longer than expected."
         # images: obs_dim is the (C, H, W) shape of one observation (dtqn.py:175-179)
@@ -265,3 +312,93 @@ class DTQN(nn.Module):
         if rc != 0:
             raise RuntimeError(f"dtqn_forward failed with DTQN status {rc}")
         return q
+
+
+class _GradRunner:
+    """One differentiable forward: the inputs as the kernels read them and the record workspace this forward owns (so the graph
+    stays valid whatever other forwards run before its backward)."""
+
+    def __init__(self, module: DTQN, obss, actions, bag_obss, bag_actions):
+        m = module
+        seq = obss.size(1)
+        assert seq <= m.history_len, "Cannot forward, history is longer than expected."
+        assert obss.dim() == 3 and obss.size(2) == m.obs_dim, f"Obs dim is incorrect. Expected {m.obs_dim} got {obss.size(2)}"
+        dev = m.flat.device
+        if dev.type != "cuda" and not getattr(m, "_allow_cpu", False):
+            raise engine.EngineUnavailable("DTQN.forward runs on the gfx950 engine only: move the module to a ROCm device")
+        self.m, self.dev, self.Bn, self.n = m, dev, int(obss.size(0)), int(seq)
+        self.obs_device, self.obs_dtype = obss.device, obss.dtype
+        self.o = obss.detach().to(device=dev, dtype=torch.float32).contiguous()
+        self.a = None
+        if m.net.action_dim > 0:
+            self.a = actions.detach().to(device=dev).reshape(self.Bn, seq).to(torch.uint8).contiguous()
+        self.bo = self.ba = None
+        if m.bag_size > 0:
+            assert bag_obss is not None and bag_obss.size(1) == m.bag_size, "bag_obss must be [B, bag_size, obs_dim]"
+            self.bo = bag_obss.detach().to(device=dev, dtype=torch.float32).contiguous()
+            if m.net.action_dim > 0:
+                self.ba = bag_actions.detach().to(device=dev).reshape(self.Bn, m.bag_size).to(torch.uint8).contiguous()
+        self.inputs = (obss, actions, bag_obss, bag_actions)
+        self.ws = None
+
+    def _stream(self):
+        return ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream) if self.dev.type == "cuda" else None
+
+    def _args(self):
+        cp = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        return cp(self.o), cp(self.a), cp(self.bo), cp(self.ba)
+
+    def forward(self) -> torch.Tensor:
+        m = self.m
+        net = m._grad_net()
+        need = int(m._lib.dtqn_grad_workspace_floats(ctypes.byref(net), self.Bn, self.n))
+        if need <= 0:
+            raise RuntimeError("dtqn_grad_workspace_floats: this network is not covered by the differentiable forward")
+        self.ws = torch.zeros(need, dtype=torch.float32, device=self.dev)
+        q = torch.empty((self.Bn, self.n, m.num_actions), dtype=torch.float32, device=self.dev)
+        rc = m._lib.dtqn_forward_train(ctypes.byref(net), ctypes.c_void_p(m.flat.data_ptr()), *self._args(), self.Bn, self.n,
+                                       ctypes.c_void_p(q.data_ptr()), ctypes.c_void_p(self.ws.data_ptr()), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"dtqn_forward_train failed with DTQN status {rc}")
+        if net is not m.net:
+            # whole-sequence shapes: the records come from the row-block twin, Q from the kernels the no-grad forward runs
+            # (the two families agree to rounding, not bit for bit)
+            obss, actions, bag_obss, bag_actions = self.inputs
+            q = m._forward_nograd(obss, actions, bag_obss, bag_actions)
+        self.inputs = None                  # the backward reads the kernels' copies (o, a, bo, ba) only
+        return q
+
+    def backward(self, dq: torch.Tensor, want_obs: bool):
+        m = self.m
+        net = m._grad_net()
+        dq = dq.detach().to(device=self.dev, dtype=torch.float32).contiguous()
+        grad = torch.zeros(m.net.n_trainable, dtype=torch.float32, device=self.dev)
+        dobs = torch.empty_like(self.o) if want_obs else None
+        cp = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        rc = m._lib.dtqn_backward_dq(ctypes.byref(net), cp(m.flat), *self._args(), self.Bn, self.n, cp(dq), cp(self.ws), cp(grad),
+                                     cp(dobs), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"dtqn_backward_dq failed with DTQN status {rc}")
+        self.ws = None                      # once_differentiable: the records are not read again
+        if dobs is not None:
+            dobs = dobs.to(device=self.obs_device, dtype=self.obs_dtype)
+        return grad, dobs
+
+
+class _DtqnForward(torch.autograd.Function):
+    """Q = DTQN.forward(obss, ...) with every unique trainable Parameter as an input; backward = dtqn_backward_dq."""
+
+    @staticmethod
+    def forward(ctx, runner: _GradRunner, obss, *params):
+        ctx.runner = runner
+        return runner.forward()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dq):
+        runner = ctx.runner
+        want_obs = ctx.needs_input_grad[1] and not runner.m.discrete
+        grad, dobs = runner.backward(dq, want_obs)
+        outs = [grad[off:off + p.numel()].view(p.shape) if ctx.needs_input_grad[2 + i] else None
+                for i, (p, off) in enumerate(runner.m._grad_params(with_offsets=True))]
+        return (None, dobs, *outs)

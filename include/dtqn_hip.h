@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define DTQN_ABI_VERSION 18
+#define DTQN_ABI_VERSION 19
 #define DTQN_MAX_LAYERS 8
 
 /* status codes */
@@ -538,6 +538,30 @@ int dtqn_img_td_lists(const DtqnNet* net, const DtqnReplay* rp, const DtqnTd* td
 /* DTQN.forward for image nets on precomputed embeddings: xemb [batch][n][D - a] (from dtqn_img_encode); otherwise as dtqn_forward_tiled */
 int dtqn_forward_tiled_pre(const DtqnNet* net, const float* theta, const float* xemb, const uint8_t* actions, int batch, int n,
                            float* q_out, float* workspace, int train_mode, uint32_t dropout_seed, uint32_t dropout_step, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Differentiable forward (torch autograd through DTQN.forward, dtqn_amd/networks/dtqn.py): DTQN.forward of dtqn.py:158-218 on
+ * caller-supplied inputs that keeps what the backward reads, and loss.backward() from an arbitrary dL/dQ.  Row-block networks
+ * (`tiled == 1`; whole-sequence shapes run on their dtqn_net_tiled_twin, same theta layout), width-padded and bag networks
+ * included; image networks return DTQN_ERR_CONFIG.  No dropout (the no-grad forward's function).  Deterministic: the same inputs give
+ * bit-identical Q, grad and dobs.
+ * ------------------------------------------------------------------------------------------ */
+/* floats of the workspace one differentiable forward of `batch` sequences of n rows keeps for its backward (0: not covered).  It is
+ * ZEROED once by the caller; a forward and the backward of its records use the same one */
+long long dtqn_grad_workspace_floats(const DtqnNet* net, int batch, int n);
+/* obs [B][n][O] f32 (discrete tokens as floats, like dtqn_forward_tiled), actions [B][n] u8 (NULL when action_dim == 0), bag_obs
+ * [B][bag_size][O] / bag_actions [B][bag_size] for bag networks (NULL otherwise): writes Q [B][n][A] -- the values dtqn_forward_tiled /
+ * dtqn_forward_bag return -- and the activation records of all B sequences into `workspace` */
+int dtqn_forward_train(const DtqnNet* net, const float* theta, const float* obs, const uint8_t* actions, const float* bag_obs,
+                       const uint8_t* bag_actions, int batch, int n, float* q_out, float* workspace, void* stream);
+/* dq [B][n][A] = dL/dQ of the last dtqn_forward_train on `workspace` (same theta and inputs)  ->
+ *   grad [n_trainable] = sum over b, t, a of dq * dQ/dtheta: WRITTEN, not accumulated; no 1/B, no clipping; padding entries 0
+ *   dobs [B][n][O] (continuous observations; NULL = not wanted) = the dq-weighted dQ/dobs.  Tokens and actions have no gradient
+ * Rows n .. padded context of the records take no part.  The TD update's kernels: data-gradient chain, split-K weight gradients in a
+ * fixed order (dtqn_td_wgrad + dtqn_td_reduce) */
+int dtqn_backward_dq(const DtqnNet* net, const float* theta, const float* obs, const uint8_t* actions, const float* bag_obs,
+                     const uint8_t* bag_actions, int batch, int n, const float* dq, float* workspace, float* grad, float* dobs,
+                     void* stream);
 
 /* Debug aid: when a device buffer of >= 2*64 int64 is registered, workgroup 0 of the forward (slots
  * 0..63) and backward (slots 64..127) TD kernels records the 100 MHz wall clock at its stage

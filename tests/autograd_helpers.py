@@ -1,0 +1,92 @@
+"""Shared by the autograd tests (tests/test_emu_autograd.py on the CPU emulation, tests/test_gpu_autograd.py on the device): a
+DTQN module with oracle weights and the differentiable forward on, random inputs, and the oracle's gradients of the same loss."""
+import numpy as np
+import torch
+
+from dtqn_amd.networks.dtqn import DTQN
+from oracle import dtqn_oracle as O
+
+from helpers import flat_from_params, pack_theta, padding_mask
+
+
+def make_module(lib, cfg: O.NetCfg, params, device="cpu", autograd=True) -> DTQN:
+    m = DTQN(cfg.obs_dim, cfg.num_actions, cfg.embed_per_obs_dim, cfg.action_dim, cfg.inner_embed_size, cfg.num_heads, cfg.num_layers,
+             cfg.history_len, dropout=cfg.dropout, gate=cfg.gate, identity=cfg.identity, pos=cfg.pos, discrete=cfg.discrete,
+             vocab_sizes=cfg.vocab_sizes if cfg.discrete else None, bag_size=cfg.bag_size, autograd=autograd, _test_lib=lib)
+    if device == "cpu":
+        m._allow_cpu = True
+    else:
+        m = m.to(device)
+    with torch.no_grad():
+        m.flat.copy_(torch.from_numpy(pack_theta(m.net, params)))
+    return m
+
+
+def make_inputs(cfg: O.NetCfg, Bn: int, n: int, seed: int):
+    """obss (float, or integer tokens as float), actions [B, n, 1], bag (or None), loss weights w [B, n, A]."""
+    rng = np.random.default_rng(seed)
+    if cfg.discrete:
+        obs = rng.integers(0, cfg.vocab_sizes, size=(Bn, n, cfg.obs_dim)).astype(np.float32)
+    else:
+        obs = rng.uniform(-1, 1, size=(Bn, n, cfg.obs_dim)).astype(np.float32)
+    act = rng.integers(0, cfg.num_actions, size=(Bn, n, 1))
+    bag = None
+    if cfg.bag_size > 0:
+        bo = rng.integers(0, cfg.vocab_sizes, size=(Bn, cfg.bag_size, cfg.obs_dim)).astype(np.float32) if cfg.discrete \
+            else rng.uniform(-1, 1, size=(Bn, cfg.bag_size, cfg.obs_dim)).astype(np.float32)
+        bag = (bo, rng.integers(0, cfg.num_actions, size=(Bn, cfg.bag_size, 1)))
+    w = rng.standard_normal((Bn, n, cfg.num_actions)).astype(np.float32)
+    return obs, act, bag, w
+
+
+def hip_grads(m: DTQN, obs, act, bag, w, device="cpu"):
+    """q, flat parameter gradient (engine layout, trainable region) and obss.grad (None for tokens) of loss = (q * w).sum()."""
+    o = torch.tensor(obs, device=device, requires_grad=not m.discrete)
+    a = torch.as_tensor(act, device=device)
+    kw = {}
+    if bag is not None:
+        kw = dict(bag_obss=torch.as_tensor(bag[0], device=device), bag_actions=torch.as_tensor(bag[1], device=device))
+    m.zero_grad(set_to_none=True)
+    q = m(o, a, **kw)
+    assert q.requires_grad and q.grad_fn is not None
+    (q * torch.as_tensor(w, device=device)).sum().backward()
+    flat = torch.zeros(m.net.n_trainable, dtype=torch.float32)
+    for p, off in m._grad_params(with_offsets=True):
+        flat[off:off + p.numel()] = p.grad.detach().reshape(-1).cpu()
+    return q.detach().cpu().numpy(), flat.numpy(), (None if o.grad is None else o.grad.cpu().numpy())
+
+
+def oracle_grads(cfg: O.NetCfg, params, obs, act, bag, w):
+    """The same loss through oracle.forward and torch.autograd.grad: q, {canonical key: grad}, d loss / d obss (continuous)."""
+    keys = O.trainable_keys(cfg)
+    leaves = {k: params[k].detach().clone().requires_grad_(True) for k in keys}
+    p2 = {k: leaves.get(O.canonical_key(cfg, k), params[k]) for k in O.state_dict_keys(cfg)}
+    o = torch.tensor(obs, dtype=torch.float32, requires_grad=True) if not cfg.discrete else torch.as_tensor(obs).long()
+    kw = {}
+    if bag is not None:
+        kw = dict(bag_obss=torch.as_tensor(bag[0]).long() if cfg.discrete else torch.as_tensor(bag[0], dtype=torch.float32),
+                  bag_actions=torch.as_tensor(bag[1]))
+    q = O.forward(p2, cfg, o, torch.as_tensor(act), **kw)
+    loss = (q * torch.as_tensor(w)).sum()
+    wrt = [leaves[k] for k in keys] + ([o] if not cfg.discrete else [])
+    g = torch.autograd.grad(loss, wrt)
+    grads = dict(zip(keys, g))
+    return q.detach().numpy(), grads, (g[-1].numpy() if not cfg.discrete else None)
+
+
+def check_against_oracle(m: DTQN, cfg, params, obs, act, bag, w, device="cpu", rtol=2e-4):
+    q, got, dobs = hip_grads(m, obs, act, bag, w, device)
+    q_ref, grads, dobs_ref = oracle_grads(cfg, params, obs, act, bag, w)
+    qmax = float(np.abs(q_ref).max())
+    assert np.abs(q - q_ref).max() <= 1e-4 * max(1.0, qmax), (np.abs(q - q_ref).max(), qmax)
+    ref = flat_from_params(m.net, grads, O.trainable_keys(cfg))
+    err = np.abs(got - ref).max()
+    assert err <= rtol * np.abs(ref).max(), (err, np.abs(ref).max())
+    pad = padding_mask(m.net)
+    if pad.any():                           # width-padded network: no gradient in the padding
+        assert not got[pad].any()
+    if dobs_ref is not None:
+        assert dobs is not None
+        derr = np.abs(dobs - dobs_ref).max()
+        assert derr <= rtol * np.abs(dobs_ref).max(), (derr, np.abs(dobs_ref).max())
+    return q, got, dobs
