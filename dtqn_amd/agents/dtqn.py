@@ -243,6 +243,20 @@ class DtqnAgent:
         return int(torch.argmax(q[0, -1]).item())
 
     @torch.no_grad()
+    def _module_action(self) -> int:
+        """get_action through DTQN.forward on the unpadded context prefix (dtqn.py:79-108): the route of a policy network with attention
+        capture on, which then holds the acting context's weights (transformer_layers[i].alpha [1, n, n]), as the reference's does."""
+        ctx = self.context
+        n = min(ctx.max_length, ctx.timestep + 1)
+        t = lambda a, dt: torch.as_tensor(a, dtype=dt, device=self.device)
+        drop = None
+        if self.train_mode == TrainMode.TRAIN and self.policy_network.dropout_p > 0.0:
+            self._actor_calls += 1
+            drop = (int(self.engine.td.dropout_seed) ^ 0xAC70, self._actor_calls)
+        q = self.policy_network(t(ctx.obs[None, :n], self.obs_tensor_type), t(ctx.action[None, :n], torch.long), _train_dropout=drop)
+        return int(torch.argmax(q[0, -1]).item())
+
+    @torch.no_grad()
     def _bag_action(self) -> int:
         """get_action of a bag network (dtqn.py:79-108): the unpadded context prefix plus the WHOLE bag, padding included."""
         ctx = self.context
@@ -258,6 +272,8 @@ class DtqnAgent:
             return self._bag_action()
         if self.image is not None:
             return self._image_action()
+        if getattr(self.policy_network, "_capture", False):
+            return self._module_action()
         self._launch_actor_forward(self.engine._stream())
         if self._main_stream is not None:
             self._main_stream.synchronize()
@@ -273,6 +289,8 @@ class DtqnAgent:
             return self._bag_action()
         if self.image is not None:
             return self._image_action()
+        if getattr(self.policy_network, "_capture", False):          # attention capture: through the module forward, like bag networks
+            return self._module_action()
         if not self._actor_stream_ok:             # CPU kernel-emulation tests: no streams, same result
             return self._sync_forward_action()
         if self._actor_stream is None:

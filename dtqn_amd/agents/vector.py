@@ -10,6 +10,9 @@ Replay semantics stay the reference's: an episode becomes sampleable when it has
 excludes the slot in progress).  With N episodes in progress at once, each environment collects its episode on the
 host and replays it into the buffer's producer API (store_obs, store x len, flush) when it ends, so the device arrays
 hold exactly what the single-environment loop would have written for that episode.
+
+Attention capture (DTQN(..., capture_attention=True)) is not done here: the batched actor launch keeps no attention records, so the
+policy network's `alpha` / `attn_weights` are those of its last module forward (DtqnAgent.get_action captures).
 """
 from __future__ import annotations
 

@@ -2335,6 +2335,115 @@ __global__ __launch_bounds__(256) void tl_attn_kb_dq_kernel(TlAttnBwdArgs a) {
     }
 }
 
+// ---- head-averaged attention weights from the differentiable forward's records (dtqn_attn_weights) ------------------------------------
+// alpha[l][b][t][s] = (1/H) sum_h P_h[t][s] for s <= t < n, 0 above the diagonal: what nn.MultiheadAttention returns as its weights with
+// average_attn_weights=True (transformer.py:64-70,88-94).  P is recomputed as the attention backward recomputes it (tl_attn_kb_dq_kernel):
+// q of the record scaled by hd_eff^-0.5 log2 e, P = exp2(q.k - lse log2 e) with the forward's natural-log row LSE -- no second softmax
+// pass.  Grid (B, lower-triangular 64 x 64 tiles of the first n rows, NL); the tile's 4 waves own 16 query rows each.  Per head, in a
+// fixed order: k rows of the key block staged through LDS, q and lse of the lane's query row straight from the record, S^T by
+// v_mfma_f32_16x16x4_f32 as attention_forward_chunk forms it (at head widths 4 / 8 that is one / two MFMA steps per 16 x 16 tile, no
+// wasted contraction), exp2 added into registers.  1/H once, then the tile goes through LDS to coalesced row stores.  The workgroup of
+// a diagonal tile also writes the zeros right of it.  No atomics: every output element has one writer.  Rows >= n of the records may
+// hold anything (pad rows): their q is not read and every masked score is replaced, not multiplied.
+struct TlAlphaArgs {
+    const float* rec;                  // act records [B][stride] of dtqn_forward_train
+    float* alpha;                      // [NL][B][n][n]
+    long long stride;
+    int layer0, layer_stride, qkv, lse;  // ao_layer0, act_layer_stride, al_qkv ([LPB][3D]), al_lse ([H][LPB])
+    int D, lpb, n, batch;
+    int heads;                         // heads averaged: the caller's real heads (DtqnNet.heads_real) on a width-padded network
+    float hd_eff;                      // head width of the softmax scale, as in TlAttnArgs
+};
+template <int HD>
+__global__ __launch_bounds__(256) void tl_alpha_kernel(TlAlphaArgs a) {
+    constexpr int LDK = HD + 4, KS = HD / 4, LDO = TL_KB + 1;
+    constexpr float LOG2E = 1.4426950408889634f;
+    constexpr int SMF = TL_KB * LDK > TL_KB * LDO ? TL_KB * LDK : TL_KB * LDO;
+    __shared__ __attribute__((aligned(16))) float SM[SMF];             // [64][k] of one head, then the [64][64] output tile
+    const Thr t = make_thr();
+    const int b = (int)blockIdx.x, l = (int)blockIdx.z;
+    int qb = 0, kb = (int)blockIdx.y;                                  // tile y -> (query block qb, key block kb <= qb), row by row
+    while (kb > qb) { kb -= qb + 1; ++qb; }
+    const float* rb = a.rec + (size_t)b * a.stride + a.layer0 + (size_t)l * a.layer_stride;
+    const float* qkv = rb + a.qkv;
+    const float* lse = rb + a.lse;
+    const int ld = 3 * a.D, trow = qb * TL_KB + t.wave * 16 + t.i;
+    const bool tlive = trow < a.n;
+    const float scale2 = LOG2E / sqrtf(a.hd_eff);
+    // diagonal tile: key tiles u > wave lie wholly above the diagonal for this wave's rows
+    const int u_hi = kb == qb ? t.wave : 3;
+    f32x4 acc[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) acc[u] = zero4();
+    for (int h = 0; h < a.heads; ++h) {
+        if (h > 0) __syncthreads();                                    // every wave is done with the previous head's keys
+        for (int idx = t.tid; idx < TL_KB * KS; idx += 256) {
+            const int r = idx / KS, c = (idx - r * KS) * 4;
+            st4(SM + r * LDK + c, ld4(qkv + (size_t)(kb * TL_KB + r) * ld + a.D + h * HD + c));
+        }
+        float qf[KS];
+        const float* qp = qkv + (size_t)trow * ld + h * HD + t.kq * KS;
+#pragma unroll
+        for (int c = 0; c < KS; ++c) qf[c] = tlive ? qp[c] * scale2 : 0.f;
+        const float lse2 = tlive ? lse[(size_t)h * a.lpb + trow] * LOG2E : 0.f;
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (u > u_hi) break;
+            const float* kp = SM + (u * 16 + t.i) * LDK + t.kq * KS;
+            f32x4 st = zero4();
+#pragma unroll
+            for (int c = 0; c < KS; ++c) st = mfma16(kp[c], qf[c], st);
+            // st[r] = S^T[s = kb*64 + u*16 + kq*4 + r][trow]
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int s = kb * TL_KB + u * 16 + t.kq * 4 + r;
+                const float p = DTQN_EXP2(st[r] - lse2);
+                acc[u][r] += (tlive && s <= trow) ? p : 0.f;
+            }
+        }
+    }
+    __syncthreads();                                                   // the key tile's LDS becomes the output tile
+    const float inv = 1.0f / (float)a.heads;
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) SM[(t.wave * 16 + t.i) * LDO + u * 16 + t.kq * 4 + r] = acc[u][r] * inv;
+    __syncthreads();
+    float* out = a.alpha + ((size_t)l * a.batch + b) * a.n * a.n;
+    const int r0 = qb * TL_KB, c0 = kb * TL_KB;
+    for (int idx = t.tid; idx < TL_KB * TL_KB; idx += 256) {
+        const int r = idx / TL_KB, c = idx - r * TL_KB;
+        if (r0 + r < a.n && c0 + c < a.n) out[(size_t)(r0 + r) * a.n + c0 + c] = SM[r * LDO + c];
+    }
+    if (kb == qb) {                                                    // the key blocks right of the diagonal: zeros
+        const int cz = c0 + TL_KB, w = a.n - cz;
+        const int rows = a.n - r0 < TL_KB ? a.n - r0 : TL_KB;
+        for (int idx = t.tid; w > 0 && idx < rows * w; idx += 256) {
+            const int r = idx / w, c = idx - r * w;
+            out[(size_t)(r0 + r) * a.n + cz + c] = 0.f;
+        }
+    }
+}
+
+// Bag attention weights averaged over heads (dtqn.py:211): out[b][t][j] = (1/H) sum_h p[b][h][t][j], t < n, j < bag.  One thread per
+// output element, the heads in a fixed order.
+struct TlBagAlphaArgs {
+    const float* rec;                  // act records [B][stride]; the weights at ao_bag_p: [H][LPB][bag_ld]
+    float* out;                        // [B][n][bag]
+    long long stride;
+    int p_off, lpb, n, bag, bag_ld, heads, total;     // total = B n bag
+};
+__global__ __launch_bounds__(256) void tl_bag_alpha_kernel(TlBagAlphaArgs a) {
+    const int idx = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (idx >= a.total) return;
+    const int j = idx % a.bag, bt = idx / a.bag, b = bt / a.n, t = bt - b * a.n;
+    const float* p = a.rec + (size_t)b * a.stride + a.p_off + (size_t)t * a.bag_ld + j;
+    float sum = 0.f;
+    for (int h = 0; h < a.heads; ++h) sum += p[(size_t)h * a.lpb * a.bag_ld];
+    a.out[idx] = sum * (1.0f / (float)a.heads);
+}
+
 // ---- LayerNorm over 64-row blocks -----------------------------------------------------------------------------------
 struct TlLnArgs {
     Fld src, dst, st;                  // st: (mean, rstd) per row, base may be null
@@ -4042,4 +4151,40 @@ extern "C" int dtqn_backward_dq(const DtqnNet* net, const float* theta, const fl
     // weight gradients: the TD update's split-K contraction over act x grd (fixed order), summed into grad by dtqn_td_reduce
     if ((rc = dtqn_td_wgrad(net, &td, stream)) != DTQN_OK) return rc;
     return dtqn_td_reduce(net, &td, stream);
+}
+
+// ---- attention weights of the last dtqn_forward_train on `workspace` (DTQN(..., capture_attention=True)) --------------------------------
+extern "C" int dtqn_attn_weights(const DtqnNet* net, const float* workspace, int batch, int n, float* alpha_out, float* bag_out,
+                                 void* stream) {
+    if (!net || !workspace || !alpha_out || batch < 1) return DTQN_ERR_ARG;
+    if (!grad_net_ok(net)) return DTQN_ERR_CONFIG;
+    if (n < 1 || n > net->ctx_len) return DTQN_ERR_ARG;
+    if (bag_out != nullptr && net->bag_size < 1) return DTQN_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    const int H = net->d_real > 0 ? net->heads_real : net->num_heads, HD = net->head_dim;
+    {
+        TlAlphaArgs a;
+        a.rec = workspace; a.alpha = alpha_out; a.stride = net->act_stride;
+        a.layer0 = net->ao_layer0; a.layer_stride = net->act_layer_stride; a.qkv = net->al_qkv; a.lse = net->al_lse;
+        a.D = net->d_model; a.lpb = net->lp; a.n = n; a.batch = batch; a.heads = H;
+        a.hd_eff = (float)(net->hd_real > 0 ? net->hd_real : HD);
+        const int nqb = (n + TL_KB - 1) / TL_KB;
+        const dim3 grid(batch, nqb * (nqb + 1) / 2, net->num_layers);
+        bool launched = false;
+#define TL_ALPHA_CASE(hd)                                                                                            \
+        if (HD == hd) { TL_LAUNCH((tl_alpha_kernel<hd>), grid, dim3(256), 0, s, a); launched = true; }
+        TL_ATTN_HEAD_DIMS(TL_ALPHA_CASE)
+#undef TL_ALPHA_CASE
+        if (!launched) return DTQN_ERR_CONFIG;
+    }
+    if (bag_out != nullptr) {
+        TlBagAlphaArgs a;
+        a.rec = workspace; a.out = bag_out; a.stride = net->act_stride; a.p_off = net->ao_bag_p;
+        a.lpb = net->lp; a.n = n; a.bag = net->bag_size; a.bag_ld = net->bag_ld; a.heads = net->num_heads;
+        const long long total = (long long)batch * n * net->bag_size;
+        if (total > 0x7fffffffLL) return DTQN_ERR_ARG;
+        a.total = (int)total;
+        TL_LAUNCH(tl_bag_alpha_kernel, dim3((a.total + 255) / 256), dim3(256), 0, s, a);
+    }
+    return DTQN_OK;
 }

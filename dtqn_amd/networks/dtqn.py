@@ -9,7 +9,9 @@ in the other (the FULL training checkpoints do not: the reference pickles joblib
 writes plain arrays) --, while the engine
 sees a single contiguous theta.  DtqnAgent.train() does not go through autograd: it runs the fused HIP
 update on these same buffers.  `DTQN(..., autograd=True)` makes `forward` differentiable for losses written in
-torch (_DtqnForward: the HIP backward of dtqn_backward_dq behind a torch.autograd.Function).
+torch (_DtqnForward: the HIP backward of dtqn_backward_dq behind a torch.autograd.Function).  `DTQN(..., capture_attention=True)`
+leaves the attention weights on the module after every forward, as the reference does (`transformer_layers[i].alpha`, and
+`attn_weights` with a bag: dtqn_attn_weights over the records of dtqn_forward_train).
 """
 from __future__ import annotations
 
@@ -29,12 +31,28 @@ class _Node(nn.Module):
     """Anonymous container used to reproduce the reference's dotted state_dict keys."""
 
 
+class _Layers(_Node):
+    """`transformer_layers`: indexable and sized like the reference's nn.Sequential (dtqn.py:120-131); children "0", "1", ..."""
+
+    def _ordered(self):
+        return [self._modules[k] for k in sorted(self._modules, key=int)]
+
+    def __len__(self) -> int:
+        return len(self._modules)
+
+    def __iter__(self):
+        return iter(self._ordered())
+
+    def __getitem__(self, idx):
+        return self._ordered()[idx]
+
+
 def _attach(root: nn.Module, dotted: str, param: nn.Parameter) -> None:
     parts = dotted.split(".")
     mod = root
     for name in parts[:-1]:
         if name not in mod._modules:
-            mod.add_module(name, _Node())
+            mod.add_module(name, _Layers() if (mod is root and name == "transformer_layers") else _Node())
         mod = mod._modules[name]
     mod.register_parameter(parts[-1], param)
 
@@ -54,11 +72,13 @@ class DTQN(nn.Module):
     def __init__(self, obs_dim: int, num_actions: int, embed_per_obs_dim: int, action_dim: int,
                  inner_embed_size: int, num_heads: int, num_layers: int, history_len: int, dropout: float = 0.0,
                  gate: str = "res", identity: bool = False, pos: Union[str, int] = "learned", discrete: bool = False,
-                 vocab_sizes: Optional[Union[np.ndarray, int]] = None, bag_size: int = 0, autograd: bool = False, _test_lib=None,
-                 **kwargs):
+                 vocab_sizes: Optional[Union[np.ndarray, int]] = None, bag_size: int = 0, autograd: bool = False,
+                 capture_attention: bool = False, _test_lib=None, **kwargs):
         super().__init__()
         # opt-in: callers of the no-grad forward use its output directly (a tensor that requires grad would break .numpy())
         self._autograd = bool(autograd)
+        # opt-in: a capturing forward keeps the training records (dtqn_forward_train) to read the attention weights from
+        self._capture = bool(capture_attention)
         image = tuple(int(v) for v in obs_dim) if isinstance(obs_dim, (tuple, list, torch.Size)) else None
         if image is not None and len(image) == 2:
             image = (1,) + image                      # representations.py:88-92: H x W means one channel
@@ -101,11 +121,21 @@ class DTQN(nn.Module):
         mask[mask.bool()] = -float("inf")
         for l in range(num_layers):
             _attach(self, f"transformer_layers.{l}.attn_mask", nn.Parameter(mask.clone(), requires_grad=False))
+        # storage for the attention weights (transformer.py:46, dtqn.py:135), written by capturing forwards only; `attn_weights`
+        # appears with the first capturing forward of a bag network, and `bag_attn_weights` stays None, as in the reference
+        for layer in self.transformer_layers:
+            layer.alpha = None
+        self.bag_attn_weights = None
         self.reset_parameters()
 
     def set_autograd(self, flag: bool) -> "DTQN":
         """Switch the differentiable forward on or off (see forward)."""
         self._autograd = bool(flag)
+        return self
+
+    def set_capture_attention(self, flag: bool) -> "DTQN":
+        """Switch attention capture on or off (see forward)."""
+        self._capture = bool(flag)
         return self
 
     # ------------------------------------------------------------------------------------------
@@ -227,7 +257,13 @@ class DTQN(nn.Module):
         -> Q [B, seq, num_actions].  No autograd graph, unless the module was built with autograd=True (or set_autograd(True)),
         grad mode is on and a trainable parameter or a continuous `obss` requires grad: then Q is the output of a
         torch.autograd.Function whose backward is the HIP backward (parameters' .grad accumulate as usual; obss.grad for
-        continuous observations).  Both compute the same Q, bit for bit (eval mode: no dropout)."""
+        continuous observations).  Both compute the same Q, bit for bit (eval mode: no dropout).
+        With capture_attention=True (or set_capture_attention(True)) every forward also stores, detached, on the device:
+        transformer_layers[i].alpha [B, seq, seq], each layer's causal attention weights averaged over heads, and with a bag
+        attn_weights [B, seq, bag_size], the bag attention averaged over heads.  Q is the same, bit for bit, as with capture off.
+        Image networks and train mode with dropout > 0 (the reference would return post-dropout weights) are refused."""
+        if self._capture:
+            self._capture_check(_train_dropout)
         if self._autograd and torch.is_grad_enabled():
             if self.image is not None:
                 raise NotImplementedError("DTQN autograd: image observations are not covered by the differentiable forward "
@@ -237,8 +273,49 @@ class DTQN(nn.Module):
             if obs_grad or any(p.requires_grad for p in params):
                 if _train_dropout is not None and self.dropout_p > 0.0:
                     raise NotImplementedError("DTQN autograd: the differentiable forward has no train-mode dropout")
-                return _DtqnForward.apply(_GradRunner(self, obss, actions, bag_obss, bag_actions), obss, *params)
+                runner = _GradRunner(self, obss, actions, bag_obss, bag_actions)
+                q = _DtqnForward.apply(runner, obss, *params)
+                if self._capture:          # the records the backward will read: no extra forward
+                    self._store_attention(runner.net, runner.ws, runner.Bn, runner.n)
+                return q
+        if self._capture:
+            return self._forward_capture(obss, actions, bag_obss, bag_actions)
         return self._forward_nograd(obss, actions, bag_obss, bag_actions, _train_dropout)
+
+    def _capture_check(self, _train_dropout) -> None:
+        if self.image is not None:
+            raise NotImplementedError("DTQN attention capture: image networks are not covered (their forward keeps no attention records)")
+        if self.dropout_p > 0.0 and (self.training or _train_dropout is not None):
+            raise NotImplementedError("DTQN attention capture: train mode with dropout > 0 is not covered (the reference would return the "
+                                      "post-dropout weights); call eval() first")
+
+    @torch.no_grad()
+    def _forward_capture(self, obss, actions, bag_obss, bag_actions) -> torch.Tensor:
+        """No-grad forward through dtqn_forward_train into a record workspace this module keeps, then the attention weights."""
+        runner = _GradRunner(self, obss, actions, bag_obss, bag_actions)
+        need = int(self._lib.dtqn_grad_workspace_floats(ctypes.byref(self._grad_net()), runner.Bn, runner.n))
+        ws = getattr(self, "_capture_ws", None)
+        if need > 0 and (ws is None or ws.numel() < need or ws.device != runner.dev):
+            ws = self._capture_ws = None            # (the old one goes before the new one is made)
+            ws = self._capture_ws = torch.zeros(need, dtype=torch.float32, device=runner.dev)
+        q = runner.forward(ws)
+        self._store_attention(runner.net, runner.ws, runner.Bn, runner.n)
+        runner.ws = None
+        return q
+
+    def _store_attention(self, net, ws: torch.Tensor, Bn: int, n: int) -> None:
+        dev = ws.device
+        alpha = torch.empty((self.net.num_layers, Bn, n, n), dtype=torch.float32, device=dev)
+        bag = torch.empty((Bn, n, self.bag_size), dtype=torch.float32, device=dev) if self.bag_size > 0 else None
+        cp = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else None
+        rc = self._lib.dtqn_attn_weights(ctypes.byref(net), cp(ws), Bn, n, cp(alpha), cp(bag), stream)
+        if rc != 0:
+            raise RuntimeError(f"dtqn_attn_weights failed with DTQN status {rc}")
+        for l, layer in enumerate(self.transformer_layers):
+            layer.alpha = alpha[l]
+        if bag is not None:
+            self.attn_weights = bag
 
     def _grad_params(self, with_offsets: bool = False):
         """Every trainable Parameter once (the shared GRU gate is one Parameter under several keys), in buffer order."""
@@ -348,13 +425,14 @@ class _GradRunner:
         cp = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
         return cp(self.o), cp(self.a), cp(self.bo), cp(self.ba)
 
-    def forward(self) -> torch.Tensor:
+    def forward(self, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """ws: a zeroed-once workspace of at least dtqn_grad_workspace_floats floats to keep the records in (None: a new one)."""
         m = self.m
-        net = m._grad_net()
+        net = self.net = m._grad_net()
         need = int(m._lib.dtqn_grad_workspace_floats(ctypes.byref(net), self.Bn, self.n))
         if need <= 0:
             raise RuntimeError("dtqn_grad_workspace_floats: this network is not covered by the differentiable forward")
-        self.ws = torch.zeros(need, dtype=torch.float32, device=self.dev)
+        self.ws = torch.zeros(need, dtype=torch.float32, device=self.dev) if ws is None else ws
         q = torch.empty((self.Bn, self.n, m.num_actions), dtype=torch.float32, device=self.dev)
         rc = m._lib.dtqn_forward_train(ctypes.byref(net), ctypes.c_void_p(m.flat.data_ptr()), *self._args(), self.Bn, self.n,
                                        ctypes.c_void_p(q.data_ptr()), ctypes.c_void_p(self.ws.data_ptr()), self._stream())

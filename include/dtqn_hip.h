@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define DTQN_ABI_VERSION 19
+#define DTQN_ABI_VERSION 20
 #define DTQN_MAX_LAYERS 8
 
 /* status codes */
@@ -562,6 +562,15 @@ int dtqn_forward_train(const DtqnNet* net, const float* theta, const float* obs,
 int dtqn_backward_dq(const DtqnNet* net, const float* theta, const float* obs, const uint8_t* actions, const float* bag_obs,
                      const uint8_t* bag_actions, int batch, int n, const float* dq, float* workspace, float* grad, float* dobs,
                      void* stream);
+/* The attention weights of the last dtqn_forward_train on `workspace` (same net, batch and n), as the reference leaves them on the
+ * module after a forward: TransformerLayer.alpha = nn.MultiheadAttention(..., average_attn_weights=True)'s weights, the causal
+ * softmax averaged over heads (transformer.py:46,64-70,88-94), and with a bag DTQN.attn_weights, the bag cross-attention averaged
+ * over heads (dtqn.py:211).
+ *   alpha_out [NL][B][n][n]: row-major, zeros above the diagonal.  Width-padded networks average over the caller's heads_real heads
+ *                            (the all-zero padding heads attend uniformly and take no part), scores scaled by 1 / sqrt(hd_real)
+ *   bag_out   [B][n][bag_size] (bag networks; NULL = not wanted)
+ * Recomputed from the q | k | v records and the row log-sum-exp (no second softmax pass); deterministic, no atomics */
+int dtqn_attn_weights(const DtqnNet* net, const float* workspace, int batch, int n, float* alpha_out, float* bag_out, void* stream);
 
 /* Debug aid: when a device buffer of >= 2*64 int64 is registered, workgroup 0 of the forward (slots
  * 0..63) and backward (slots 64..127) TD kernels records the 100 MHz wall clock at its stage
