@@ -135,6 +135,8 @@ def load_library(path: str) -> ctypes.CDLL:
         "dtqn_grad_workspace_floats": [P(DtqnNet), i32, i32],
         "dtqn_forward_train": [P(DtqnNet), vp, vp, vp, vp, vp, i32, i32, vp, vp, vp],
         "dtqn_backward_dq": [P(DtqnNet), vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp],
+        "dtqn_forward_train_drop": [P(DtqnNet), vp, vp, vp, vp, vp, i32, i32, vp, vp, u32, i32, vp],
+        "dtqn_backward_dq_drop": [P(DtqnNet), vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, u32, i32, vp],
         "dtqn_attn_weights": [P(DtqnNet), vp, i32, i32, vp, vp, vp],
         "dtqn_xch_publish": [vp, i32, vp],
         "dtqn_td_xreduce": [P(DtqnNet), P(DtqnTd), vp, vp, i32, i32, vp, vp, vp, vp],

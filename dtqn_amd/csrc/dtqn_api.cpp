@@ -215,3 +215,14 @@ extern "C" int dtqn_actor_forward_batch(const DtqnNet* net, const float* theta, 
     int32_t* xflags = split ? reinterpret_cast<int32_t*>(workspace + dtqn_td_xch_floats(net, n_envs)) : nullptr;
     return dtqn::forward_infer(net, theta, obs, actions, n_envs, n_max, q_dev, q_last_host, stream, xch, xflags, lens, L, dropout_seed, dropout_step, train_mode);
 }
+
+// The differentiable forward without dropout (the function the no-grad forward computes): the _drop entry points with the masks off.
+extern "C" int dtqn_forward_train(const DtqnNet* net, const float* theta, const float* obs, const uint8_t* actions, const float* bag_obs,
+                                  const uint8_t* bag_actions, int batch, int n, float* q_out, float* workspace, void* stream) {
+    return dtqn_forward_train_drop(net, theta, obs, actions, bag_obs, bag_actions, batch, n, q_out, workspace, 0u, -1, stream);
+}
+extern "C" int dtqn_backward_dq(const DtqnNet* net, const float* theta, const float* obs, const uint8_t* actions, const float* bag_obs,
+                                const uint8_t* bag_actions, int batch, int n, const float* dq, float* workspace, float* grad, float* dobs,
+                                void* stream) {
+    return dtqn_backward_dq_drop(net, theta, obs, actions, bag_obs, bag_actions, batch, n, dq, workspace, grad, dobs, 0u, -1, stream);
+}

@@ -4077,8 +4077,11 @@ extern "C" long long dtqn_grad_workspace_floats(const DtqnNet* net, int batch, i
     return grad_ws(*net, batch).total;
 }
 
-extern "C" int dtqn_forward_train(const DtqnNet* net, const float* theta, const float* obs, const uint8_t* actions, const float* bag_obs,
-                                  const uint8_t* bag_actions, int batch, int n, float* q_out, float* workspace, void* stream) {
+// dropout_step >= 0 with net->dropout > 0: a train-mode forward -- one pass (pass 0) of `batch` sequences, keep masks keyed by
+// (dropout_seed, dropout_step, 0, b, site, layer, element), the key of the TD update's training third.  dropout_step < 0: no dropout
+extern "C" int dtqn_forward_train_drop(const DtqnNet* net, const float* theta, const float* obs, const uint8_t* actions, const float* bag_obs,
+                                       const uint8_t* bag_actions, int batch, int n, float* q_out, float* workspace, uint32_t dropout_seed,
+                                       int32_t dropout_step, void* stream) {
     if (!net || !theta || !obs || !q_out || !workspace || batch < 1) return DTQN_ERR_ARG;
     if (!grad_net_ok(net)) return DTQN_ERR_CONFIG;          // whole-sequence nets: their dtqn_net_tiled_twin; image nets: not covered
     if (n < 1 || n > net->ctx_len) return DTQN_ERR_ARG;     // dtqn.py:170-173
@@ -4091,18 +4094,20 @@ extern "C" int dtqn_forward_train(const DtqnNet* net, const float* theta, const 
     src.bag_obs = bag_obs; src.bag_actions = bag_actions; src.bag_batch = batch;
     const long long qs = (long long)n * net->num_actions;
     hipStream_t s = (hipStream_t)stream;
-    // no dropout: the function the no-grad forward computes (its default), with the records of a training forward
+    // without dropout: the function the no-grad forward computes (its default), with the records of a training forward
+    const TlDrop drop = tl_drop_make(*net, dropout_seed, (uint32_t)dropout_step, nullptr, batch, dropout_step >= 0 ? 0x1 : 0);
     switch (net->d_model) {
-        case 64: return forward_records<64>(*net, theta, theta, batch, src, batch, n, workspace, true, q_out, qs, net->num_actions, s, tl_drop_none());
-        case 128: return forward_records<128>(*net, theta, theta, batch, src, batch, n, workspace, true, q_out, qs, net->num_actions, s, tl_drop_none());
-        case 256: return forward_records<256>(*net, theta, theta, batch, src, batch, n, workspace, true, q_out, qs, net->num_actions, s, tl_drop_none());
+        case 64: return forward_records<64>(*net, theta, theta, batch, src, batch, n, workspace, true, q_out, qs, net->num_actions, s, drop);
+        case 128: return forward_records<128>(*net, theta, theta, batch, src, batch, n, workspace, true, q_out, qs, net->num_actions, s, drop);
+        case 256: return forward_records<256>(*net, theta, theta, batch, src, batch, n, workspace, true, q_out, qs, net->num_actions, s, drop);
         default: return DTQN_ERR_CONFIG;
     }
 }
 
-extern "C" int dtqn_backward_dq(const DtqnNet* net, const float* theta, const float* obs, const uint8_t* actions, const float* bag_obs,
-                                const uint8_t* bag_actions, int batch, int n, const float* dq, float* workspace, float* grad, float* dobs,
-                                void* stream) {
+// (dropout_seed, dropout_step): the key the forward of these records was given; the keep masks are recomputed from it
+extern "C" int dtqn_backward_dq_drop(const DtqnNet* net, const float* theta, const float* obs, const uint8_t* actions, const float* bag_obs,
+                                     const uint8_t* bag_actions, int batch, int n, const float* dq, float* workspace, float* grad, float* dobs,
+                                     uint32_t dropout_seed, int32_t dropout_step, void* stream) {
     if (!net || !theta || !obs || !dq || !workspace || !grad || batch < 1) return DTQN_ERR_ARG;
     if (!grad_net_ok(net)) return DTQN_ERR_CONFIG;
     if (n < 1 || n > net->ctx_len) return DTQN_ERR_ARG;
@@ -4130,7 +4135,7 @@ extern "C" int dtqn_backward_dq(const DtqnNet* net, const float* theta, const fl
     in.src.ep_idx = nullptr; in.src.start = nullptr; in.src.batch = batch;
     in.src.bag_obs = bag_obs; in.src.bag_actions = bag_actions; in.src.bag_batch = batch;
     in.n = n;
-    in.drop = tl_drop_none();
+    in.drop = tl_drop_make(*net, dropout_seed, (uint32_t)dropout_step, nullptr, batch, dropout_step >= 0 ? 0x1 : 0);
     int rc;
     switch (net->d_model) {
         case 64: rc = backward_records<64>(*net, in, td, s); break;

@@ -9,7 +9,8 @@ in the other (the FULL training checkpoints do not: the reference pickles joblib
 writes plain arrays) --, while the engine
 sees a single contiguous theta.  DtqnAgent.train() does not go through autograd: it runs the fused HIP
 update on these same buffers.  `DTQN(..., autograd=True)` makes `forward` differentiable for losses written in
-torch (_DtqnForward: the HIP backward of dtqn_backward_dq behind a torch.autograd.Function).  `DTQN(..., capture_attention=True)`
+torch (_DtqnForward: the HIP backward of dtqn_backward_dq behind a torch.autograd.Function; with `set_dropout_seed` a train-mode
+module applies its dropout there too, dtqn_forward_train_drop / dtqn_backward_dq_drop).  `DTQN(..., capture_attention=True)`
 leaves the attention weights on the module after every forward, as the reference does (`transformer_layers[i].alpha`, and
 `attn_weights` with a bag: dtqn_attn_weights over the records of dtqn_forward_train).
 """
@@ -90,6 +91,8 @@ class DTQN(nn.Module):
         self.obs_dim, self.discrete, self.history_len, self.bag_size = (image if image is not None else obs_dim), discrete, history_len, bag_size
         self.image = image
         self.dropout_p = float(dropout)
+        # set_dropout_seed: off by default (a forward without keep-mask keys runs without dropout, whatever self.training says)
+        self._drop_seed, self._drop_step = None, 0
         self.num_actions = num_actions
         self.net = B.make_net(self._lib, obs_dim=1 if image is not None else obs_dim, image=image, num_actions=num_actions, embed_per_obs_dim=embed_per_obs_dim,
                               action_dim=action_dim, inner_embed_size=inner_embed_size, num_heads=num_heads,
@@ -137,6 +140,31 @@ class DTQN(nn.Module):
         """Switch attention capture on or off (see forward)."""
         self._capture = bool(flag)
         return self
+
+    def set_dropout_seed(self, seed: Optional[int], step: int = 0) -> "DTQN":
+        """Train-mode dropout for forwards called on the module itself.  Once a seed is set, every forward of a module in train mode
+        with dropout > 0 -- differentiable or not -- draws the engine's keep masks for (seed, step) and advances step by one; the
+        backward of a differentiable forward recomputes the masks of ITS forward.  eval() forwards draw none and leave the counter
+        alone.  `set_dropout_seed(None)` turns it off again; setting the same (seed, step) replays the same masks."""
+        if seed is None:
+            self._drop_seed, self._drop_step = None, 0
+        else:
+            if int(step) < 0:
+                raise ValueError(f"dropout step has to be >= 0, but got {step}")
+            self._drop_seed, self._drop_step = int(seed) & 0xFFFFFFFF, int(step)
+        return self
+
+    def _dropout_keys(self, _train_dropout) -> Optional[tuple]:
+        """(seed, step) of this forward's keep masks, or None: the caller's keys, else the module's own counter in train mode."""
+        if self.dropout_p <= 0.0:
+            return None
+        if _train_dropout is not None:
+            return int(_train_dropout[0]) & 0xFFFFFFFF, int(_train_dropout[1]) & 0x7FFFFFFF
+        if self._drop_seed is None or not self.training:
+            return None
+        keys = (self._drop_seed, self._drop_step & 0x7FFFFFFF)
+        self._drop_step += 1
+        return keys
 
     # ------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -257,13 +285,17 @@ class DTQN(nn.Module):
         -> Q [B, seq, num_actions].  No autograd graph, unless the module was built with autograd=True (or set_autograd(True)),
         grad mode is on and a trainable parameter or a continuous `obss` requires grad: then Q is the output of a
         torch.autograd.Function whose backward is the HIP backward (parameters' .grad accumulate as usual; obss.grad for
-        continuous observations).  Both compute the same Q, bit for bit (eval mode: no dropout).
+        continuous observations).  Both compute the same Q, bit for bit.  Dropout is applied only to a forward that has keep-mask
+        keys: `_train_dropout=(seed, step)` (the agent's train-mode forwards), or the module's own counter once set_dropout_seed was
+        called and the module is in train mode; the differentiable and the no-grad forward draw the same masks for the same keys
+        (row-block kernels for both; a whole-sequence shape runs such a forward on its row-block twin).
         With capture_attention=True (or set_capture_attention(True)) every forward also stores, detached, on the device:
         transformer_layers[i].alpha [B, seq, seq], each layer's causal attention weights averaged over heads, and with a bag
         attn_weights [B, seq, bag_size], the bag attention averaged over heads.  Q is the same, bit for bit, as with capture off.
         Image networks and train mode with dropout > 0 (the reference would return post-dropout weights) are refused."""
         if self._capture:
             self._capture_check(_train_dropout)
+        keys = self._dropout_keys(_train_dropout)
         if self._autograd and torch.is_grad_enabled():
             if self.image is not None:
                 raise NotImplementedError("DTQN autograd: image observations are not covered by the differentiable forward "
@@ -271,16 +303,16 @@ class DTQN(nn.Module):
             params = self._grad_params()
             obs_grad = obss.requires_grad and not self.discrete
             if obs_grad or any(p.requires_grad for p in params):
-                if _train_dropout is not None and self.dropout_p > 0.0:
-                    raise NotImplementedError("DTQN autograd: the differentiable forward has no train-mode dropout")
-                runner = _GradRunner(self, obss, actions, bag_obss, bag_actions)
+                runner = _GradRunner(self, obss, actions, bag_obss, bag_actions, keys)
                 q = _DtqnForward.apply(runner, obss, *params)
                 if self._capture:          # the records the backward will read: no extra forward
                     self._store_attention(runner.net, runner.ws, runner.Bn, runner.n)
                 return q
         if self._capture:
             return self._forward_capture(obss, actions, bag_obss, bag_actions)
-        return self._forward_nograd(obss, actions, bag_obss, bag_actions, _train_dropout)
+        if keys is not None and self.image is None and self.bag_size == 0:
+            return self._forward_dropout(obss, actions, keys)
+        return self._forward_nograd(obss, actions, bag_obss, bag_actions, keys)
 
     def _capture_check(self, _train_dropout) -> None:
         if self.image is not None:
@@ -300,6 +332,20 @@ class DTQN(nn.Module):
             ws = self._capture_ws = torch.zeros(need, dtype=torch.float32, device=runner.dev)
         q = runner.forward(ws)
         self._store_attention(runner.net, runner.ws, runner.Bn, runner.n)
+        runner.ws = None
+        return q
+
+    @torch.no_grad()
+    def _forward_dropout(self, obss, actions, keys) -> torch.Tensor:
+        """No-grad train-mode forward of a network without bag or images: the differentiable forward's kernels and masks
+        (dtqn_forward_train_drop) into a record workspace this module keeps; nothing reads the records."""
+        runner = _GradRunner(self, obss, actions, None, None, keys)
+        need = int(self._lib.dtqn_grad_workspace_floats(ctypes.byref(self._grad_net()), runner.Bn, runner.n))
+        ws = getattr(self, "_drop_ws", None)
+        if need > 0 and (ws is None or ws.numel() < need or ws.device != runner.dev):
+            ws = self._drop_ws = None            # (the old one goes before the new one is made)
+            ws = self._drop_ws = torch.zeros(need, dtype=torch.float32, device=runner.dev)
+        q = runner.forward(ws)
         runner.ws = None
         return q
 
@@ -395,8 +441,10 @@ class _GradRunner:
     """One differentiable forward: the inputs as the kernels read them and the record workspace this forward owns (so the graph
     stays valid whatever other forwards run before its backward)."""
 
-    def __init__(self, module: DTQN, obss, actions, bag_obss, bag_actions):
+    def __init__(self, module: DTQN, obss, actions, bag_obss, bag_actions, keys: Optional[tuple] = None):
         m = module
+        # (seed, step) of this forward's keep masks, kept for its backward; None: no dropout (step -1 in the C ABI)
+        self.seed, self.step = keys if keys is not None else (0, -1)
         seq = obss.size(1)
         assert seq <= m.history_len, "Cannot forward, history is longer than expected."
         assert obss.dim() == 3 and obss.size(2) == m.obs_dim, f"Obs dim is incorrect. Expected {m.obs_dim} got {obss.size(2)}"
@@ -434,13 +482,15 @@ class _GradRunner:
             raise RuntimeError("dtqn_grad_workspace_floats: this network is not covered by the differentiable forward")
         self.ws = torch.zeros(need, dtype=torch.float32, device=self.dev) if ws is None else ws
         q = torch.empty((self.Bn, self.n, m.num_actions), dtype=torch.float32, device=self.dev)
-        rc = m._lib.dtqn_forward_train(ctypes.byref(net), ctypes.c_void_p(m.flat.data_ptr()), *self._args(), self.Bn, self.n,
-                                       ctypes.c_void_p(q.data_ptr()), ctypes.c_void_p(self.ws.data_ptr()), self._stream())
+        rc = m._lib.dtqn_forward_train_drop(ctypes.byref(net), ctypes.c_void_p(m.flat.data_ptr()), *self._args(), self.Bn, self.n,
+                                            ctypes.c_void_p(q.data_ptr()), ctypes.c_void_p(self.ws.data_ptr()), self.seed, self.step,
+                                            self._stream())
         if rc != 0:
-            raise RuntimeError(f"dtqn_forward_train failed with DTQN status {rc}")
-        if net is not m.net:
+            raise RuntimeError(f"dtqn_forward_train_drop failed with DTQN status {rc}")
+        if net is not m.net and self.step < 0:
             # whole-sequence shapes: the records come from the row-block twin, Q from the kernels the no-grad forward runs
-            # (the two families agree to rounding, not bit for bit)
+            # (the two families agree to rounding, not bit for bit).  Under dropout Q stays the twin's: Q and the records the
+            # backward reads then come from the same masks, drawn once
             obss, actions, bag_obss, bag_actions = self.inputs
             q = m._forward_nograd(obss, actions, bag_obss, bag_actions)
         self.inputs = None                  # the backward reads the kernels' copies (o, a, bo, ba) only
@@ -453,10 +503,10 @@ class _GradRunner:
         grad = torch.zeros(m.net.n_trainable, dtype=torch.float32, device=self.dev)
         dobs = torch.empty_like(self.o) if want_obs else None
         cp = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
-        rc = m._lib.dtqn_backward_dq(ctypes.byref(net), cp(m.flat), *self._args(), self.Bn, self.n, cp(dq), cp(self.ws), cp(grad),
-                                     cp(dobs), self._stream())
+        rc = m._lib.dtqn_backward_dq_drop(ctypes.byref(net), cp(m.flat), *self._args(), self.Bn, self.n, cp(dq), cp(self.ws), cp(grad),
+                                          cp(dobs), self.seed, self.step, self._stream())
         if rc != 0:
-            raise RuntimeError(f"dtqn_backward_dq failed with DTQN status {rc}")
+            raise RuntimeError(f"dtqn_backward_dq_drop failed with DTQN status {rc}")
         self.ws = None                      # once_differentiable: the records are not read again
         if dobs is not None:
             dobs = dobs.to(device=self.obs_device, dtype=self.obs_dtype)
@@ -464,11 +514,13 @@ class _GradRunner:
 
 
 class _DtqnForward(torch.autograd.Function):
-    """Q = DTQN.forward(obss, ...) with every unique trainable Parameter as an input; backward = dtqn_backward_dq."""
+    """Q = DTQN.forward(obss, ...) with every unique trainable Parameter as an input; backward = dtqn_backward_dq_drop with the
+    forward's own (seed, step), which travel in ctx with the runner."""
 
     @staticmethod
     def forward(ctx, runner: _GradRunner, obss, *params):
         ctx.runner = runner
+        ctx.dropout_keys = (runner.seed, runner.step)
         return runner.forward()
 
     @staticmethod

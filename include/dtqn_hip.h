@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define DTQN_ABI_VERSION 20
+#define DTQN_ABI_VERSION 21
 #define DTQN_MAX_LAYERS 8
 
 /* status codes */
@@ -543,8 +543,9 @@ int dtqn_forward_tiled_pre(const DtqnNet* net, const float* theta, const float* 
  * Differentiable forward (torch autograd through DTQN.forward, dtqn_amd/networks/dtqn.py): DTQN.forward of dtqn.py:158-218 on
  * caller-supplied inputs that keeps what the backward reads, and loss.backward() from an arbitrary dL/dQ.  Row-block networks
  * (`tiled == 1`; whole-sequence shapes run on their dtqn_net_tiled_twin, same theta layout), width-padded and bag networks
- * included; image networks return DTQN_ERR_CONFIG.  No dropout (the no-grad forward's function).  Deterministic: the same inputs give
- * bit-identical Q, grad and dobs.
+ * included; image networks return DTQN_ERR_CONFIG.  dtqn_forward_train / dtqn_backward_dq run without dropout (the no-grad forward's
+ * function); the _drop forms below add train-mode dropout.  Deterministic: the same inputs (and mask key) give bit-identical Q, grad
+ * and dobs.
  * ------------------------------------------------------------------------------------------ */
 /* floats of the workspace one differentiable forward of `batch` sequences of n rows keeps for its backward (0: not covered).  It is
  * ZEROED once by the caller; a forward and the backward of its records use the same one */
@@ -562,6 +563,19 @@ int dtqn_forward_train(const DtqnNet* net, const float* theta, const float* obs,
 int dtqn_backward_dq(const DtqnNet* net, const float* theta, const float* obs, const uint8_t* actions, const float* bag_obs,
                      const uint8_t* bag_actions, int batch, int n, const float* dq, float* workspace, float* grad, float* dobs,
                      void* stream);
+/* Train-mode dropout (nn.Dropout / MultiheadAttention(dropout=p) of a module in train mode: dtqn.py:105,196, transformer.py:34,41, bag
+ * attention dtqn.py:136-141) in the differentiable forward.  dropout_step >= 0 with net->dropout > 0: every site -- embedding, attention
+ * weights, feed-forward output, bag attention weights -- takes the keep mask the TD update's training third draws, the counter-based
+ * hash of (dropout_seed, dropout_step, pass 0, sequence b, site, layer, element); dtqn_backward_dq_drop recomputes the masks from the
+ * same key (the caller keeps the two integers with the workspace; nothing else is stored), so grad and dobs are the gradients of the
+ * masked function.  dropout_step < 0, or net->dropout == 0: dtqn_forward_train / dtqn_backward_dq, bit for bit (they are these calls
+ * with dropout_step = -1).  Rows n .. padded context draw no mask that reaches a live row (masks are keyed by the element's own row) */
+int dtqn_forward_train_drop(const DtqnNet* net, const float* theta, const float* obs, const uint8_t* actions, const float* bag_obs,
+                            const uint8_t* bag_actions, int batch, int n, float* q_out, float* workspace, uint32_t dropout_seed,
+                            int32_t dropout_step, void* stream);
+int dtqn_backward_dq_drop(const DtqnNet* net, const float* theta, const float* obs, const uint8_t* actions, const float* bag_obs,
+                          const uint8_t* bag_actions, int batch, int n, const float* dq, float* workspace, float* grad, float* dobs,
+                          uint32_t dropout_seed, int32_t dropout_step, void* stream);
 /* The attention weights of the last dtqn_forward_train on `workspace` (same net, batch and n), as the reference leaves them on the
  * module after a forward: TransformerLayer.alpha = nn.MultiheadAttention(..., average_attn_weights=True)'s weights, the causal
  * softmax averaged over heads (transformer.py:46,64-70,88-94), and with a bag DTQN.attn_weights, the bag cross-attention averaged
