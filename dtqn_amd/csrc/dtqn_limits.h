@@ -18,6 +18,12 @@ static inline size_t dtqn_attn_tile_lds(int lp, int hd, int bwd) {
 }
 static inline int dtqn_attn_whole_tile(int lp, int hd) { return dtqn_attn_tile_lds(lp, hd, 1) <= 160 * 1024; }
 
+// Bag attention (dtqn_tiled.hip): the resident kernels (tl_bag_attn_kernel, tl_bag_attn_bwd_kernel) hold the bag's k | v rows of one head
+// in LDS and, in the backward, an [n][bag] dS tile beside them (n = 0: the forward's request).  A bag whose backward request at the full
+// context exceeds 160 KB runs the matrix-core kernels instead (tl_bag_attn_mfma_*: 64 bag entries or 64 query rows at a time).
+static inline size_t dtqn_bag_attn_lds(int n, int bag, int hd) { return ((size_t)2 * bag * hd + (size_t)n * bag) * sizeof(float); }
+static inline int dtqn_bag_attn_resident(int ctx, int bag, int hd) { return dtqn_bag_attn_lds(ctx, bag, hd) <= 160 * 1024; }
+
 // The whole-sequence kernels exist as explicit instantiations <d_model, 16-row tiles, head_dim, waves> (dtqn_forward.hip:
 // dispatch_fwd, dtqn_backward.hip: td_backward): X(d, mt, hd, nw).  TRAIN = forward and backward exist; the first entry of a
 // (d, mt, hd) is the default wave count, the others are reached with DTQN_WAVES (A/B switch).  dtqn_net_init places a network on

@@ -2925,7 +2925,8 @@ __global__ __launch_bounds__(256) void tl_dobs_kernel(TlDobsArgs a) {
 }
 
 // ---- bag attention (dtqn.py:211-213): nn.MultiheadAttention(query = working memory, key = value = bag embeddings), no mask ----
-// One workgroup per (sequence, head); the bag is at most a few dozen entries, so this is plain VALU code out of LDS.
+// One workgroup per (sequence, head), plain VALU code out of LDS: the kernels of the bags whose backward tile (k | v and an [n][bag] dS
+// tile) fits LDS, which is every bag of a few dozen entries.  Larger bags run tl_bag_attn_mfma_* below (tl_bag_mfma).
 struct TlBagAttnArgs {
     Fld q;                             // [LPB][D]   W_q xf + b_q
     Fld kv;                            // [LPB][2D]  k | v of the bag entries (rows < bag)
@@ -2977,6 +2978,7 @@ __global__ __launch_bounds__(256) void tl_bag_attn_kernel(TlBagAttnArgs a) {
 // backward: dP = dO v^T, dS = P (dP - sum_j P dP), dq = scale dS k, dk = scale dS^T q, dv = P^T dO
 struct TlBagAttnBwdArgs {
     Fld q, kv, p, dO;                  // dO: [LPB][D] gradient of the attention output
+    Fld o;                             // [LPB][D] the forward's attention output (read by tl_bag_attn_mfma_*: delta = rowsum(dO o))
     Fld dq;                            // [LPB][D]
     Fld dkv;                           // [LPB][2D] (rows < bag written)
     int D, HD, n, bag, bag_ld, lpb;
@@ -3028,6 +3030,350 @@ __global__ __launch_bounds__(256) void tl_bag_attn_bwd_kernel(TlBagAttnBwdArgs a
         float* row = frow(a.dkv, s, j);
         row[h * HD + c] = dk;
         row[a.D + h * HD + c] = dv;
+    }
+}
+
+// ---- bag attention on the matrix core (bags whose resident backward tile does not fit LDS: dtqn_bag_attn_resident) ---------------------
+// Built like the key-blocked kernels (tl_attn_kb_*): wave w of a workgroup owns 16-row tile w of a 64-row block, the other operand is
+// staged 64 rows at a time through static LDS, every product is a v_mfma_f32_16x16x4_f32 with the scores TRANSPOSED (lane (i, kq) holds
+// bag entries kq*4 + r of query row i, see attention_forward_chunk).  There is no causal mask; entries >= bag of the last partial block
+// are masked by replacement and the staged rows >= bag / >= n are zeros, so nothing a pad row of a record holds reaches a sum.  Nothing
+// resident grows with n * bag, no float atomics, one writer per output element, a fixed summation order.
+// rows [j0, j0 + 64) of the bag's k | v (NP = 2) or k alone (NP = 1) of head h -> KV[64][2 HD + 4]
+template <int HD, int NP>
+__device__ __forceinline__ void tl_bag_stage(float* KV, const Fld& kv, int s, int h, int D, int j0, int bag, const Thr& t) {
+    constexpr int LDK = 2 * HD + 4, C4 = HD / 4;
+    for (int idx = t.tid; idx < TL_KB * NP * C4; idx += 256) {
+        const int r = idx / (NP * C4), rem = idx - r * (NP * C4);
+        const int which = rem / C4, c = (rem - which * C4) * 4;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (j0 + r < bag) v = ld4(frow(kv, s, j0 + r) + which * D + h * HD + c);
+        st4(KV + r * LDK + which * HD + c, v);
+    }
+}
+// st[u][r] = S^T[j0 + u*16 + kq*4 + r][this lane's query row] in the log2 domain (qf is pre-scaled); -inf at entries >= bag
+template <int HD>
+__device__ __forceinline__ void tl_bag_scores(const float* KV, const float (&qf)[HD / 4], int j0, int bag, const Thr& t, f32x4 (&st)[4]) {
+    constexpr int LDK = 2 * HD + 4, KS = HD / 4;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        st[u] = zero4();
+        if (j0 + u * 16 < bag) {                                       // (wave-uniform: tiles wholly beyond the bag cost nothing)
+            const float* kp = KV + (u * 16 + t.i) * LDK + t.kq * KS;
+#pragma unroll
+            for (int c = 0; c < KS; ++c) st[u] = mfma16(kp[c], qf[c], st[u]);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            if (j0 + u * 16 + t.kq * 4 + r >= bag) st[u][r] = -INFINITY;
+    }
+}
+// Forward: grid (S, H, LPB / 64), query block z.  q of the lane's row in registers, pre-scaled by hd^-0.5 log2 e; online softmax over the
+// bag blocks (one pair of kq reductions per block); a training forward then writes the pre-dropout weights exp2(s - m) / l of the final
+// (m, l) into the ao_bag_p record from a RECOMPUTED score pass (k alone restaged; a bag of one block is still in LDS): no scratch, no
+// per-block statistics to keep.  Query rows >= n produce zeros and leave the weight record alone.
+template <int HD, bool DROP>
+__global__ __launch_bounds__(256) void tl_bag_attn_mfma_kernel(TlBagAttnArgs a) {
+    constexpr int LDK = 2 * HD + 4, KS = HD / 4, CT = (HD + 15) / 16;
+    __shared__ __attribute__((aligned(16))) float KV[TL_KB * LDK];     // [64][k | v] of this head
+    const Thr t = make_thr();
+    const int s = (int)blockIdx.x, h = (int)blockIdx.y, qb = (int)blockIdx.z;
+    const int trow = qb * TL_KB + t.wave * 16 + t.i;
+    float* op = frow(a.o, s, trow) + h * HD;
+    if (qb * TL_KB >= a.n) {                                           // pad rows only
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct)
+            if (ct * 16 + t.kq * 4 < HD) st4(op + ct * 16 + t.kq * 4, make_float4(0.f, 0.f, 0.f, 0.f));
+        return;
+    }
+    const bool live = trow < a.n, live_tile = qb * TL_KB + t.wave * 16 < a.n;
+    const float scale = 1.4426950408889634f / sqrtf((float)HD);
+    float qf[KS];
+    const float* qp = frow(a.q, s, trow) + h * HD + t.kq * KS;
+#pragma unroll
+    for (int c = 0; c < KS; ++c) qf[c] = live ? qp[c] * scale : 0.f;
+    f32x4 acc[CT][2];
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) { acc[ct][0] = zero4(); acc[ct][1] = zero4(); }
+    float m = -INFINITY, l = 0.f;
+    Drop dr = drop_off();
+    if constexpr (DROP) dr = tl_drop(a.drop, s);
+    const int nbb = (a.bag + TL_KB - 1) / TL_KB;
+    for (int jb = 0; jb < nbb; ++jb) {
+        if (jb > 0) __syncthreads();                                   // every wave is done with the previous block
+        const int j0 = jb * TL_KB;
+        tl_bag_stage<HD, 2>(KV, a.kv, s, h, a.D, j0, a.bag, t);
+        __syncthreads();
+        if (!live_tile) continue;
+        f32x4 st[4];
+        tl_bag_scores<HD>(KV, qf, j0, a.bag, t, st);
+        float tmax = st[0][0];
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) tmax = fmaxf(tmax, st[u][r]);
+        const float mn = fmaxf(m, kq_max(tmax));                       // finite: entry j0 of a block is inside the bag
+        float ps = 0.f;
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) { st[u][r] = DTQN_EXP2(st[u][r] - mn); ps += st[u][r]; }
+        ps = kq_sum(ps);
+        if (jb > 0) {
+            const float corr = DTQN_EXP2(m - mn);
+            l = l * corr + ps;
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { acc[ct][0][e] *= corr; acc[ct][1][e] *= corr; }
+        } else {
+            l = ps;
+        }
+        m = mn;
+        if (dr.thresh != 0u) {                                         // the row sum above is of the undropped weights
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    st[u][r] = drop_keep(dr, DROP_BAG, 0, drop_attn_idx(h, trow, j0 + u * 16 + t.kq * 4 + r)) ? st[u][r] * dr.scale : 0.f;
+        }
+        // O^T[c][t] += V^T[c][j] P^T[j][t]
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (j0 + u * 16 >= a.bag) break;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float* vp = KV + (u * 16 + t.kq * 4 + r) * LDK + HD;
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct) {
+                    const int c = ct * 16 + t.i;
+                    acc[ct][r & 1] = mfma16(vp[c < HD ? c : 0], st[u][r], acc[ct][r & 1]);
+                }
+            }
+        }
+    }
+    const float inv = live ? 1.0f / l : 0.f;
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) {
+        const int c = ct * 16 + t.kq * 4;
+        if (c < HD)
+            st4(op + c, make_float4((acc[ct][0][0] + acc[ct][1][0]) * inv, (acc[ct][0][1] + acc[ct][1][1]) * inv,
+                                    (acc[ct][0][2] + acc[ct][1][2]) * inv, (acc[ct][0][3] + acc[ct][1][3]) * inv));
+    }
+    if (a.p.base == nullptr) return;
+    // the weights BEFORE dropout, for the backward, tl_bag_alpha_kernel and attention capture
+    float* prow = a.p.base + (size_t)s * a.p.stride + ((size_t)h * a.lpb + trow) * a.bag_ld;
+    for (int jb = 0; jb < nbb; ++jb) {
+        const int j0 = jb * TL_KB;
+        if (nbb > 1) {
+            __syncthreads();
+            tl_bag_stage<HD, 1>(KV, a.kv, s, h, a.D, j0, a.bag, t);
+            __syncthreads();
+        }
+        if (!live_tile) continue;
+        f32x4 st[4];
+        tl_bag_scores<HD>(KV, qf, j0, a.bag, t, st);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int j = j0 + u * 16 + t.kq * 4;                      // j < bag: j + 3 < bag_ld (a multiple of 4); masked entries store 0
+            if (live && j < a.bag)
+                st4(prow + j, make_float4(DTQN_EXP2(st[u][0] - m) * inv, DTQN_EXP2(st[u][1] - m) * inv,
+                                          DTQN_EXP2(st[u][2] - m) * inv, DTQN_EXP2(st[u][3] - m) * inv));
+        }
+    }
+}
+
+// Backward.  dP = dO v^T by MFMA, the weights P from the forward's record, dS = P (dP_masked - delta) with
+// delta[t] = sum_j P dP_masked = sum_c dO[t][c] o[t][c] (o is the forward's output of the DROPPED weights, so the identity holds under
+// dropout too; tl_attn_kb_rows takes the same sum) -- no sweep over the whole bag before the first dS, nothing handed from one kernel to
+// the other.
+// dq = scale dS k: grid (S, H, LPB / 64), query block z; dO of the lane's row in registers, k | v of the bag blocks staged in turn.
+template <int HD, bool DROP>
+__global__ __launch_bounds__(256) void tl_bag_attn_mfma_dq_kernel(TlBagAttnBwdArgs a) {
+    constexpr int LDK = 2 * HD + 4, KS = HD / 4, CT = (HD + 15) / 16;
+    __shared__ __attribute__((aligned(16))) float KV[TL_KB * LDK];     // [64][k | v] of this head
+    const Thr t = make_thr();
+    const int s = (int)blockIdx.x, h = (int)blockIdx.y, qb = (int)blockIdx.z;
+    const int trow = qb * TL_KB + t.wave * 16 + t.i;
+    float* dqp = frow(a.dq, s, trow) + h * HD;
+    if (qb * TL_KB >= a.n) {                                           // pad rows: dq = 0
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct)
+            if (ct * 16 + t.kq * 4 < HD) st4(dqp + ct * 16 + t.kq * 4, make_float4(0.f, 0.f, 0.f, 0.f));
+        return;
+    }
+    const bool live = trow < a.n, live_tile = qb * TL_KB + t.wave * 16 < a.n;
+    const float scale = 1.0f / sqrtf((float)HD);
+    float dof[KS], part = 0.f;
+    {
+        const float* dp = frow(a.dO, s, trow) + h * HD + t.kq * KS;
+        const float* og = frow(a.o, s, trow) + h * HD + t.kq * KS;
+#pragma unroll
+        for (int c = 0; c < KS; ++c) {
+            dof[c] = live ? dp[c] : 0.f;
+            part = fmaf(dof[c], live ? og[c] : 0.f, part);
+        }
+    }
+    const float delta = kq_sum(part);
+    f32x4 acc[CT][2];
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) { acc[ct][0] = zero4(); acc[ct][1] = zero4(); }
+    Drop dr = drop_off();
+    if constexpr (DROP) dr = tl_drop(a.drop, s);
+    const float* prow = a.p.base + (size_t)s * a.p.stride + ((size_t)h * a.lpb + trow) * a.bag_ld;
+    const int nbb = (a.bag + TL_KB - 1) / TL_KB;
+    for (int jb = 0; jb < nbb; ++jb) {
+        if (jb > 0) __syncthreads();
+        const int j0 = jb * TL_KB;
+        tl_bag_stage<HD, 2>(KV, a.kv, s, h, a.D, j0, a.bag, t);
+        __syncthreads();
+        if (!live_tile) continue;
+#pragma unroll 1
+        for (int u = 0; u < 4; ++u) {
+            if (j0 + u * 16 >= a.bag) break;
+            const float* vp = KV + (u * 16 + t.i) * LDK + HD + t.kq * KS;
+            f32x4 dp = zero4();
+#pragma unroll
+            for (int c = 0; c < KS; ++c) dp = mfma16(vp[c], dof[c], dp);
+            // dp[r] = dP[trow][j + r]
+            const int j = j0 + u * 16 + t.kq * 4;
+            const float4 p4 = live && j < a.bag ? ld4(prow + j) : make_float4(0.f, 0.f, 0.f, 0.f);
+            const float p[4] = {p4.x, p4.y, p4.z, p4.w};
+            float ds[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float dpm = dr.thresh == 0u ? dp[r] : (drop_keep(dr, DROP_BAG, 0, drop_attn_idx(h, trow, j + r)) ? dp[r] * dr.scale : 0.f);
+                ds[r] = live && j + r < a.bag ? p[r] * (dpm - delta) : 0.f;
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float* krow = KV + (u * 16 + t.kq * 4 + r) * LDK;
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct) {
+                    const int c = ct * 16 + t.i;
+                    acc[ct][r & 1] = mfma16(krow[c < HD ? c : 0], ds[r], acc[ct][r & 1]);
+                }
+            }
+        }
+    }
+    const float f = live ? scale : 0.f;
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) {
+        const int c = ct * 16 + t.kq * 4;
+        if (c < HD)
+            st4(dqp + c, make_float4((acc[ct][0][0] + acc[ct][1][0]) * f, (acc[ct][0][1] + acc[ct][1][1]) * f,
+                                     (acc[ct][0][2] + acc[ct][1][2]) * f, (acc[ct][0][3] + acc[ct][1][3]) * f));
+    }
+}
+// dk = scale dS^T q, dv = P_dropped^T dO: grid (S, H, ceil(bag / 64)), bag block z; v of the lane's entry in registers, q | dO, the P rows
+// and delta of the query blocks with live rows staged in turn (rows >= n as zeros).  Only rows < bag of dkv are written.
+template <int HD, bool DROP>
+__global__ __launch_bounds__(256) void tl_bag_attn_mfma_dkv_kernel(TlBagAttnBwdArgs a) {
+    constexpr int LDK = 2 * HD + 4, KS = HD / 4, CT = (HD + 15) / 16, C4 = HD / 4, LDP = TL_KB + 4;
+    __shared__ __attribute__((aligned(16))) float QD[TL_KB * LDK];     // [64][q | dO] of this head
+    __shared__ __attribute__((aligned(16))) float Ps[TL_KB * LDP];     // [64 query rows][64 entries of this bag block]
+    __shared__ __attribute__((aligned(16))) float delta_s[TL_KB * 4];  // [64 query rows][4 partial sums of dO o]
+    const Thr t = make_thr();
+    const int s = (int)blockIdx.x, h = (int)blockIdx.y, j0 = (int)blockIdx.z * TL_KB;
+    const int jrow = j0 + t.wave * 16 + t.i;
+    const bool jlive = jrow < a.bag, live_tile = j0 + t.wave * 16 < a.bag;
+    const float scale = 1.0f / sqrtf((float)HD);
+    float vf[KS];
+    {
+        const float* vp = frow(a.kv, s, jlive ? jrow : 0) + a.D + h * HD + t.kq * KS;
+#pragma unroll
+        for (int c = 0; c < KS; ++c) vf[c] = jlive ? vp[c] : 0.f;
+    }
+    f32x4 acck[CT][2], accv[CT][2];
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) { acck[ct][0] = zero4(); acck[ct][1] = zero4(); accv[ct][0] = zero4(); accv[ct][1] = zero4(); }
+    Drop dr = drop_off();
+    if constexpr (DROP) dr = tl_drop(a.drop, s);
+    const float* pbase = a.p.base + (size_t)s * a.p.stride + (size_t)h * a.lpb * a.bag_ld;
+    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int q0 = 0; q0 < a.n; q0 += TL_KB) {
+        if (q0 > 0) __syncthreads();
+        for (int idx = t.tid; idx < TL_KB * 2 * C4; idx += 256) {
+            const int r = idx / (2 * C4), rem = idx - r * (2 * C4);
+            const int which = rem / C4, c = (rem - which * C4) * 4;
+            float4 v = z4;
+            if (q0 + r < a.n) v = ld4((which == 0 ? frow(a.q, s, q0 + r) : frow(a.dO, s, q0 + r)) + h * HD + c);
+            st4(QD + r * LDK + which * HD + c, v);
+        }
+        for (int idx = t.tid; idx < TL_KB * (TL_KB / 4); idx += 256) {
+            const int r = idx / (TL_KB / 4), c = (idx - r * (TL_KB / 4)) * 4;
+            float4 v = z4;
+            if (q0 + r < a.n && j0 + c < a.bag) v = ld4(pbase + (size_t)(q0 + r) * a.bag_ld + j0 + c);
+            st4(Ps + r * LDP + c, v);
+        }
+        {   // delta partials in the dq kernel's order: thread (row, kq) sums its KS columns, the reader adds (p0 + p2) + (p1 + p3) as kq_sum does
+            const int r = t.tid >> 2, kq = t.tid & 3;
+            float p = 0.f;
+            if (q0 + r < a.n) {
+                const float* og = frow(a.o, s, q0 + r) + h * HD + kq * KS;
+                const float* dg = frow(a.dO, s, q0 + r) + h * HD + kq * KS;
+#pragma unroll
+                for (int c = 0; c < KS; ++c) p = fmaf(dg[c], og[c], p);
+            }
+            delta_s[t.tid] = p;
+        }
+        __syncthreads();
+        if (!live_tile) continue;
+#pragma unroll 1
+        for (int u = 0; u < 4; ++u) {
+            const int t0 = q0 + u * 16;
+            if (t0 >= a.n) break;
+            const float* dop = QD + (u * 16 + t.i) * LDK + HD + t.kq * KS;
+            f32x4 dp = zero4();
+#pragma unroll
+            for (int c = 0; c < KS; ++c) dp = mfma16(dop[c], vf[c], dp);
+            // dp[r] = dP[t0 + kq*4 + r][jrow]
+            float del4[4], ds[4], pd[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float4 d4 = ld4(delta_s + (u * 16 + t.kq * 4 + r) * 4);
+                del4[r] = (d4.x + d4.z) + (d4.y + d4.w);
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int tr = t0 + t.kq * 4 + r;
+                const bool on = jlive && tr < a.n;
+                const float p = Ps[(u * 16 + t.kq * 4 + r) * LDP + t.wave * 16 + t.i];
+                float dpm = dp[r], pk = p;
+                if (dr.thresh != 0u) {
+                    const bool keep = drop_keep(dr, DROP_BAG, 0, drop_attn_idx(h, tr, jrow));
+                    dpm = keep ? dp[r] * dr.scale : 0.f;
+                    pk = keep ? p * dr.scale : 0.f;                    // dv takes the dropped weights
+                }
+                ds[r] = on ? p * (dpm - del4[r]) : 0.f;
+                pd[r] = on ? pk : 0.f;
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float* qrow = QD + (u * 16 + t.kq * 4 + r) * LDK;
+                const float* dorow = qrow + HD;
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct) {
+                    const int c = ct * 16 + t.i;
+                    const int cc = c < HD ? c : 0;
+                    acck[ct][r & 1] = mfma16(qrow[cc], ds[r], acck[ct][r & 1]);
+                    accv[ct][r & 1] = mfma16(dorow[cc], pd[r], accv[ct][r & 1]);
+                }
+            }
+        }
+    }
+    if (!jlive) return;
+    float* kout = frow(a.dkv, s, jrow) + h * HD;
+    float* vout = kout + a.D;
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) {
+        const int c = ct * 16 + t.kq * 4;
+        if (c < HD) {
+            st4(kout + c, make_float4((acck[ct][0][0] + acck[ct][1][0]) * scale, (acck[ct][0][1] + acck[ct][1][1]) * scale,
+                                      (acck[ct][0][2] + acck[ct][1][2]) * scale, (acck[ct][0][3] + acck[ct][1][3]) * scale));
+            st4(vout + c, make_float4(accv[ct][0][0] + accv[ct][1][0], accv[ct][0][1] + accv[ct][1][1],
+                                      accv[ct][0][2] + accv[ct][1][2], accv[ct][0][3] + accv[ct][1][3]));
+        }
     }
 }
 // dst[rows][cols] = src[rows][cols] (any leading dims): the working-memory half of d xcat -> the stream gradient
@@ -3312,6 +3658,54 @@ static int launch_attn_bwd(const TlAttnBwdArgs& a, int S, int H, int HD, hipStre
     if (HD == hd) {                                                                                                  \
         if (a.drop.thresh != 0u) TL_LAUNCH((tl_attn_bwd_kernel<hd, true>), dim3(S, H), dim3(256), lds, stream, a);   \
         else TL_LAUNCH((tl_attn_bwd_kernel<hd, false>), dim3(S, H), dim3(256), lds, stream, a);                      \
+        return DTQN_OK;                                                                                              \
+    }
+    TL_ATTN_HEAD_DIMS(TL_ATTN_CASE)
+#undef TL_ATTN_CASE
+    return DTQN_ERR_CONFIG;
+}
+
+// Bag attention: the matrix-core kernels (tl_bag_attn_mfma_*) take over exactly where the resident backward's LDS request at the network's
+// full context does not fit a workgroup (dtqn_bag_attn_resident) -- by ctx_len and not by the live row count of one call, so that every
+// forward and backward of a network runs the same family; DTQN_BAG_ATTN_MFMA=1 (A/B and tests, read per launch) forces them on any bag.
+static inline bool tl_bag_mfma(const DtqnNet& net) {
+    const char* e = getenv("DTQN_BAG_ATTN_MFMA");
+    return (e != nullptr && e[0] == '1') || !dtqn_bag_attn_resident(net.ctx_len, net.bag_size, net.head_dim);
+}
+static int launch_bag_attn(const DtqnNet& net, const TlBagAttnArgs& a, int S, hipStream_t stream) {
+    const int H = net.num_heads, HD = net.head_dim;
+    if (!tl_bag_mfma(net)) {
+        TL_LAUNCH(tl_bag_attn_kernel, dim3(S, H), dim3(256), dtqn_bag_attn_lds(0, a.bag, HD), stream, a);
+        return DTQN_OK;
+    }
+    const dim3 grid(S, H, a.lpb / TL_KB);
+#define TL_ATTN_CASE(hd)                                                                                             \
+    if (HD == hd) {                                                                                                  \
+        if (a.drop.thresh != 0u) TL_LAUNCH((tl_bag_attn_mfma_kernel<hd, true>), grid, dim3(256), 0, stream, a);      \
+        else TL_LAUNCH((tl_bag_attn_mfma_kernel<hd, false>), grid, dim3(256), 0, stream, a);                         \
+        return DTQN_OK;                                                                                              \
+    }
+    TL_ATTN_HEAD_DIMS(TL_ATTN_CASE)
+#undef TL_ATTN_CASE
+    return DTQN_ERR_CONFIG;
+}
+static int launch_bag_attn_bwd(const DtqnNet& net, const TlBagAttnBwdArgs& a, int S, hipStream_t stream) {
+    const int H = net.num_heads, HD = net.head_dim;
+    if (!tl_bag_mfma(net)) {
+        TL_LAUNCH(tl_bag_attn_bwd_kernel, dim3(S, H), dim3(256), dtqn_bag_attn_lds(a.n, a.bag, HD), stream, a);
+        return DTQN_OK;
+    }
+    // dk | dv, then dq: both read only the forward's records and dO, and write disjoint fields
+    const dim3 gkv(S, H, (a.bag + TL_KB - 1) / TL_KB), gq(S, H, a.lpb / TL_KB);
+#define TL_ATTN_CASE(hd)                                                                                             \
+    if (HD == hd) {                                                                                                  \
+        if (a.drop.thresh != 0u) {                                                                                   \
+            TL_LAUNCH((tl_bag_attn_mfma_dkv_kernel<hd, true>), gkv, dim3(256), 0, stream, a);                        \
+            TL_LAUNCH((tl_bag_attn_mfma_dq_kernel<hd, true>), gq, dim3(256), 0, stream, a);                          \
+        } else {                                                                                                     \
+            TL_LAUNCH((tl_bag_attn_mfma_dkv_kernel<hd, false>), gkv, dim3(256), 0, stream, a);                       \
+            TL_LAUNCH((tl_bag_attn_mfma_dq_kernel<hd, false>), gq, dim3(256), 0, stream, a);                         \
+        }                                                                                                            \
         return DTQN_OK;                                                                                              \
     }
     TL_ATTN_HEAD_DIMS(TL_ATTN_CASE)
@@ -3650,7 +4044,7 @@ static int forward_records(const DtqnNet& net, const float* theta_a, const float
             at.q = F(rm.bag_q, D); at.kv = F(rm.bag_kv, 2 * D); at.o = F(rm.bag_o, D);
             at.p = training ? F(net.ao_bag_p, net.bag_ld) : nofld();
             at.D = D; at.HD = HD; at.n = n; at.bag = bag; at.bag_ld = net.bag_ld; at.lpb = lpb; at.drop = drop;
-            TL_LAUNCH(tl_bag_attn_kernel, dim3(S, H), dim3(256), (size_t)2 * bag * HD * sizeof(float), stream, at);
+            if ((rc = launch_bag_attn(net, at, S, stream)) != DTQN_OK) return rc;
         }
         if ((rc = linear(F(rm.bag_o, D), D, D, net.off_bag_out_w, net.off_bag_out_b, F(rm.xcat + D, 2 * D), 0, nofld(), nofld())) != DTQN_OK) return rc;
         if ((rc = linear(xw, 2 * D, D, net.off_head1_w, net.off_head1_b, F(rm.hh, D), 1, nofld(), nofld())) != DTQN_OK) return rc;
@@ -3780,9 +4174,9 @@ static int backward_records(const DtqnNet& net, const BwdIn& in, const DtqnTd& t
         {
             TlBagAttnBwdArgs at;
             at.q = FA(net.ao_bag_q, D); at.kv = FA(net.ao_bag_kv, 2 * D); at.p = FA(net.ao_bag_p, net.bag_ld); at.dO = FG(net.go_bag_do, D);
-            at.dq = FG(net.go_bag_dq, D); at.dkv = FG(net.go_bag_dkv, 2 * D);
+            at.o = FA(net.ao_bag_o, D); at.dq = FG(net.go_bag_dq, D); at.dkv = FG(net.go_bag_dkv, 2 * D);
             at.D = D; at.HD = HD; at.n = L; at.bag = bag; at.bag_ld = net.bag_ld; at.lpb = lpb; at.drop = drop;
-            TL_LAUNCH(tl_bag_attn_bwd_kernel, dim3(B, H), dim3(256), ((size_t)2 * bag * HD + (size_t)L * bag) * sizeof(float), stream, at);
+            if ((rc = launch_bag_attn_bwd(net, at, B, stream)) != DTQN_OK) return rc;
         }
         if ((rc = dx(FG(net.go_bag_dq, D), D, net.off_bag_in_w, D, G, 2, nofld())) != DTQN_OK) return rc;                  // + dq W_q
         if ((rc = dx(FG(net.go_bag_dkv, 2 * D), 2 * D, net.off_bag_in_w + D * D, D, FG(net.go_bag_de, D), 0, nofld())) != DTQN_OK) return rc;   // d E_bag
