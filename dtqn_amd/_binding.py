@@ -132,6 +132,10 @@ def load_library(path: str) -> ctypes.CDLL:
         "dtqn_img_backward": [P(DtqnNet), vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp],
         "dtqn_img_td_lists": [P(DtqnNet), P(DtqnReplay), P(DtqnTd), vp, vp, vp, vp, vp, vp, vp],
         "dtqn_forward_tiled_pre": [P(DtqnNet), vp, vp, vp, i32, i32, vp, vp, i32, u32, u32, vp],
+        "dtqn_img_actor_stage_bytes": [P(DtqnNet), i32],
+        "dtqn_img_actor_workspace_floats": [P(DtqnNet), i32],
+        "dtqn_img_actor_forward_batch": [P(DtqnNet), vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, u32, u32, vp],
+        "dtqn_debug_last_img_actor_tokens": [],
         "dtqn_grad_workspace_floats": [P(DtqnNet), i32, i32],
         "dtqn_forward_train": [P(DtqnNet), vp, vp, vp, vp, vp, i32, i32, vp, vp, vp],
         "dtqn_backward_dq": [P(DtqnNet), vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp],
@@ -154,7 +158,8 @@ def load_library(path: str) -> ctypes.CDLL:
         fn.argtypes = argtypes
         fn.restype = ctypes.c_char_p if name == "dtqn_build_info" else (
             ctypes.c_longlong if name in ("dtqn_img_act_floats", "dtqn_img_gact_floats", "dtqn_img_wpart_floats",
-                                                    "dtqn_grad_workspace_floats") else ctypes.c_int)
+                                                    "dtqn_grad_workspace_floats", "dtqn_img_actor_stage_bytes",
+                                                    "dtqn_img_actor_workspace_floats") else ctypes.c_int)
     assert set(protos) == set(FUNCTIONS), sorted(set(protos) ^ set(FUNCTIONS))
     if lib.dtqn_abi_version() != DEFINES["DTQN_ABI_VERSION"]:
         raise OSError(f"{path}: ABI version {lib.dtqn_abi_version()} != header {DEFINES['DTQN_ABI_VERSION']}")

@@ -11,6 +11,17 @@ excludes the slot in progress).  With N episodes in progress at once, each envir
 host and replays it into the buffer's producer API (store_obs, store x len, flush) when it ends, so the device arrays
 hold exactly what the single-environment loop would have written for that episode.
 
+Pixel observations (agent.image) take the same route with the window kept on the DEVICE: the frames of the N rolling contexts live
+in a ring [N][L][C H W] of uint8 and their embeddings in a second ring [N][L][d_model], so a vector step stages the N newest frames
+only, and `dtqn_img_actor_forward_batch` encodes only the frames whose embedding is not current -- the N new ones while the policy
+parameters stand still, every live one after they moved.  (run.py queues N updates behind every vector step and evaluates and
+prepopulates through the single-environment actor, so there every step re-encodes; the reuse serves callers that drive a VectorActor
+with frozen parameters or with fewer updates than steps.)  A vector step on which every environment explores only pushes its frames.  The host keeps
+(slot of the newest frame, live rows, which embeddings are current) per environment and drops the last of these whenever the
+parameters can have changed: an optimizer launch (TdEngine.updates), a host-side write to the flat buffer or to one of the
+Parameters that view it (their torch `_version`: load_state_dict, a checkpoint restore, an in-place op), a re-bound buffer.  The target network has its own
+buffer, so target_update does not touch them; embedding dropout acts behind the ring, so a change of train / eval mode does not either.
+
 Attention capture (DTQN(..., capture_attention=True)) is not done here: the batched actor launch keeps no attention records, so the
 policy network's `alpha` / `attn_weights` are those of its last module forward (DtqnAgent.get_action captures).
 """
@@ -28,23 +39,41 @@ from ..utils.context import Context
 from ..utils.random import RNG
 
 
+class _FrameContext:
+    """Host side of one image environment's rolling context: the step count.  The frames themselves are in the device ring (the frame
+    of step t sits in slot t mod L) and, until the episode ends, in VectorActor.episodes."""
+
+    def __init__(self, context_length: int):
+        self.max_length, self.timestep = context_length, 0
+
+    def reset(self, obs) -> None:
+        self.timestep = 0
+
+    def add_transition(self, o, a, r, done):
+        self.timestep += 1
+        return None, None
+
+
 class VectorActor:
     def __init__(self, agent, envs: Sequence, ref_quirks: bool = False):
-        if getattr(agent, "image", None) is not None:
-            # pixel observations act through DTQN.forward (convolutional embedding + row-block forward, one environment at a time);
-            # the float32 staging and dtqn_actor_forward_batch below have no image path
-            raise NotImplementedError("vectorised rollout of image observations (use --num-envs 1)")
         self.agent, self.envs = agent, list(envs)
         N = self.n = len(self.envs)
         L, O, A = agent.context_len, agent.env_obs_length, agent.num_actions
         self.L, self.O, self.A = L, O, A
+        self.image = getattr(agent, "image", None)
+        self.episodes = [[] for _ in range(N)]            # per env: [first_obs, (obs, action, reward, done), ...]
+        self.returns = np.zeros(N)
+        self.steps = 0
+        self.episodes_done = 0
+        self.bags = None
+        if self.image is not None:
+            self._init_image()
+            return
         self.contexts: List[Context] = [Context(L, agent.obs_mask, A, O, discrete=agent.is_discrete_env, ref_quirks=ref_quirks)
                                         for _ in range(N)]
         # bag networks: one bag per environment (utils/bag.py; dtqn.py:66-74 keeps one per agent because it steps one environment)
         self.bags = [Bag(agent.bag.size, agent.obs_mask, O, discrete=agent.is_discrete_env, ref_quirks=ref_quirks)
                      for _ in range(N)] if agent.bag.size > 0 else None
-        self.episodes = [[] for _ in range(N)]            # per env: [first_obs, (obs, action, reward, done), ...]
-        self.returns = np.zeros(N)
         cuda = agent.device.type == "cuda"
         obs_bytes = N * L * O * 4
         act_bytes = (N * L + 3) & ~3
@@ -65,8 +94,50 @@ class VectorActor:
         self._ws_p = ctypes.c_void_p(self._ws.data_ptr()) if need > 0 else None
         self._p = [ctypes.c_void_p(t.data_ptr()) for t in (self._ctx_h, self._ctx_d, self._q_d, self._q_h)]
         self._ev = torch.cuda.Event() if cuda else None      # completion of the batched actor forward alone
-        self.steps = 0
-        self.episodes_done = 0
+
+    def _init_image(self) -> None:
+        """Device rings, the pinned block of a vector step and the workspace of dtqn_img_actor_forward_batch (include/dtqn_hip.h)."""
+        from ..image import ImageEncoder
+        agent, N, L, A = self.agent, self.n, self.L, self.A
+        if agent.bag.size > 0:
+            raise NotImplementedError("vectorised rollout of image observations with a bag")
+        for env in self.envs:
+            # the block carries raw uint8 pixels (what the replay and the reference's context hold): asked once, here; staging a frame
+            # of another dtype is refused by the copy itself
+            dt = getattr(getattr(env, "observation_space", None), "dtype", None)
+            if dt is not None and np.dtype(dt) != np.uint8:
+                raise TypeError(f"image observations must be uint8 pixels, the environment declares {np.dtype(dt)}")
+        eng = agent.engine
+        lib, net_ref, dev = eng.lib, eng._actor_net_ref, agent.device
+        cuda = dev.type == "cuda"
+        O, D = int(np.prod(self.image)), int(eng.actor_net.d_model)
+        stage_bytes, need = int(lib.dtqn_img_actor_stage_bytes(net_ref, N)), int(lib.dtqn_img_actor_workspace_floats(net_ref, N))
+        if stage_bytes <= 0 or need <= 0:
+            raise NotImplementedError("vectorised rollout of image observations: this network shape is not covered")
+        pin = (lambda t: t.pin_memory()) if cuda else (lambda t: t)
+        self.contexts = [_FrameContext(L) for _ in range(N)]
+        self._stage_h = pin(torch.zeros(stage_bytes, dtype=torch.uint8))
+        buf = self._stage_h.numpy()
+        ints = buf[:stage_bytes - N * O].view(np.int32)
+        self._head_np, self._len_np, self._fresh_np = ints[:N], ints[N:2 * N], ints[2 * N:3 * N]
+        self._valid_np = ints[3 * N:3 * N + N * L].reshape(N, L)
+        self._frames_np = buf[stage_bytes - N * O:].reshape(N, O)
+        self._valid = np.zeros((N, L), dtype=np.int32)       # which embedding ring rows are current (the block gets a copy per step)
+        self._pushed = np.full(N, -1, dtype=np.int64)        # step of the newest frame each environment has in the ring (-1: none)
+        self._param_version = None
+        self._prep_due = False                               # the encoder's transposed weights are older than the parameters
+        self._params = list(agent.policy_network.parameters())
+        self._frame_ring = torch.zeros(N * L * O, dtype=torch.uint8, device=dev)
+        self._emb_ring = torch.zeros(N * L * D, dtype=torch.float32, device=dev)
+        self._enc = ImageEncoder(lib, eng.actor_net, dev)    # the transposed weights, refreshed once per parameter version
+        self._ws = torch.zeros(need, dtype=torch.float32, device=dev)
+        self._q_d = torch.zeros(N * L * A, device=dev)
+        self._q_h = pin(torch.zeros(N, A))
+        self._q_np = self._q_h.numpy()
+        self._p = [ctypes.c_void_p(t.data_ptr()) for t in (self._enc.wprep, self._stage_h, self._frame_ring, self._emb_ring, self._q_d,
+                                                           self._q_h, self._ws)]
+        self._ev = torch.cuda.Event() if cuda else None
+        self._inflight = False
 
     # ------------------------------------------------------------------------------------------
     def reset_all(self) -> None:
@@ -80,10 +151,61 @@ class VectorActor:
             self.bags[i].reset()
         self.episodes[i] = [np.array(obs, copy=True)]
         self.returns[i] = 0.0
+        if self.image is not None:
+            self._pushed[i] = -1
+            self._valid[i] = 0
+
+    def _launch_q_image(self, push_only: bool = False) -> None:
+        """Stage the newest frame of every environment and launch the batched image actor forward (no synchronisation).
+        push_only: a vector step on which every environment explores -- the frames go to the ring, nothing is encoded or forwarded
+        (their embeddings stay marked as missing and are made by the next full launch)."""
+        a, eng, L = self.agent, self.agent.engine, self.L
+        if self._inflight and self._ev is not None:
+            self._ev.synchronize()              # the kernels of the last launch read the pinned block in place
+        # (a Parameter that was re-pointed at a moved flat buffer keeps a version counter of its own: both are asked)
+        version = (eng.updates, eng.theta_pol._version, eng.theta_pol.data_ptr(), sum(p._version for p in self._params))
+        refresh = version != self._param_version
+        if refresh:
+            self._valid[:] = 0
+            self._param_version = version
+        for i, ctx in enumerate(self.contexts):
+            t = ctx.timestep
+            n, head = min(L, t + 1), t % L
+            fresh = 0
+            if self._pushed[i] != t:
+                if self._pushed[i] != t - 1:
+                    raise RuntimeError("the context moved by more than one frame since the last actor launch")
+                last = self.episodes[i][-1]
+                np.copyto(self._frames_np[i], (last if isinstance(last, np.ndarray) else last[0]).reshape(-1), casting="no")
+                self._valid[i, head] = 0
+                self._pushed[i] = t
+                fresh = 1
+            self._head_np[i], self._len_np[i], self._fresh_np[i] = head, n, fresh
+        self._valid_np[:] = self._valid
+        p = self._p
+        if push_only:
+            self._prep_due = self._prep_due or refresh
+            rc = eng.lib.dtqn_img_actor_forward_batch(eng._actor_net_ref, None, None, 0, p[1], p[2], None, self.n, None, None, None, 0, 0, 0, eng._stream())
+        else:
+            a._actor_calls += 1
+            rc = eng.lib.dtqn_img_actor_forward_batch(eng._actor_net_ref, a._theta_p, p[0], 1 if (refresh or self._prep_due) else 0, p[1], p[2], p[3],
+                                                      self.n, p[4], p[5], p[6], 1 if a.train_mode.name == "TRAIN" else 0,
+                                                      eng.td.dropout_seed ^ 0xAC70, a._actor_calls & 0xFFFFFFFF, eng._stream())
+        if rc != 0:
+            raise RuntimeError(f"dtqn_img_actor_forward_batch failed with DTQN status {rc}")
+        if not push_only:
+            self._prep_due = False
+            for i, ctx in enumerate(self.contexts):        # behind this launch every live row holds a current embedding
+                self._valid[i, :min(L, ctx.timestep + 1)] = 1
+        if self._ev is not None:
+            self._ev.record(a._main_stream)
+        self._inflight = True
 
     def _launch_q(self) -> None:
         """Stage all N contexts and launch the batched actor forward on the learner's stream (no synchronisation)."""
         a, eng = self.agent, self.agent.engine
+        if self.image is not None:
+            return self._launch_q_image()
         if self.bags is not None:
             # bag networks: the module forward with the N bags (dtqn_forward_bag); every sequence runs the longest prefix, the
             # rows behind a shorter one cannot reach its last live row (causal), its own bag attends row by row
@@ -132,6 +254,7 @@ class VectorActor:
     def _wait_q(self) -> np.ndarray:
         if self._ev is not None:
             self._ev.synchronize()              # the forward only: work queued behind it (TD updates) keeps running
+        self._inflight = False
         return self._q_np
 
     def q_values(self) -> np.ndarray:
@@ -148,6 +271,8 @@ class VectorActor:
         greedy = not explore.all()
         if greedy:
             self._launch_q()
+        elif self.image is not None:               # image contexts live in the device ring: this step's frames go there, nothing else runs
+            self._launch_q_image(push_only=True)
         if between is not None:
             between()
         if greedy:

@@ -924,3 +924,226 @@ extern "C" int dtqn_img_td_lists(const DtqnNet* net, const DtqnReplay* rp, const
     IMG_LAUNCH(img_lists_kernel, (n + IT - 1) / IT, 0, (hipStream_t)stream, a);
     return DTQN_OK;
 }
+
+// ---- vectorised rollout of image observations (dtqn_amd/agents/vector.py) --------------------------------------------------------------
+// N environments, one library call per vector step.  The frames of every rolling context live in a device ring [N][L][O] u8 and their
+// embeddings in a second ring [N][L][D] f32 with the same row numbering, so a vector step uploads the N newest frames only and encodes
+// only the frames whose embedding is not current (the new ones, or all live ones after the parameters moved).  Five stages on one stream:
+//   ring push  ->  token lists  ->  dtqn_img_encode (into the embedding ring)  ->  gather + row-block forward  ->  Q rows to pinned memory.
+// The pinned block of a step: int32 head[N] | len[N] | fresh[N] | valid[N][L] (padded to 16 bytes), then the newest frames [N][O] u8.
+// head_i: ring slot of environment i's newest frame, len_i: live rows of its window, fresh_i: the block carries a frame for slot head_i,
+// valid[i][s]: embedding ring row (i, s) was written under the current parameters.  Window row r of environment i is ring slot
+// (head_i - (len_i - 1) + r) mod L.  The kernels read the block in place (device-mapped memory, like dtqn_replay_push).
+namespace dtqn {
+
+constexpr int kImgActorChunk = 64;       // tokens per encoder pass: one row block of the Linear, and a feature-map workspace of at most
+                                         // 64 x 3.8 MB = 244 MB at 144 x 144 pixels
+
+static inline size_t img_actor_state_ints(int n_envs, int L) { return (((size_t)n_envs * (3 + L)) + 3) & ~(size_t)3; }
+
+struct ImgActorWs {
+    long long fwd, xemb, ints, act, total;      // float offsets
+};
+static inline ImgActorWs img_actor_ws(const DtqnNet& net, int n_envs) {
+    auto up4 = [](long long v) { return (v + 3) & ~3LL; };
+    const long long rows = (long long)n_envs * net.ctx_len;
+    ImgActorWs w;
+    const long long fwd = dtqn_forward_workspace_floats(&net, n_envs);
+    w.fwd = 0;
+    if (fwd <= 0) {                       // (the query's "not covered / does not fit an int": nothing may be laid out behind it)
+        w.xemb = w.ints = w.act = w.total = 0;
+        return w;
+    }
+    w.xemb = up4(fwd);
+    w.ints = w.xemb + up4(rows * net.d_model);
+    w.act = w.ints + up4(2 * rows + 2LL * n_envs);                // img_index | dst | win0[N] | len[N]
+    w.total = w.act + up4(dtqn_img_act_floats(&net, (int)(rows < kImgActorChunk ? rows : kImgActorChunk)));
+    return w;
+}
+
+struct ImgRingArgs {
+    const int32_t* state;
+    const uint8_t* frames;     // [N][O], pinned host memory
+    uint8_t* ring;             // [N][L][O]
+    int n_envs, L, O, blocks_per_env;
+};
+// 16 bytes per thread; frames whose size is no multiple of 16 go byte by byte (their rows are not 16-byte aligned in either array)
+__global__ __launch_bounds__(IT) void img_ring_push_kernel(ImgRingArgs a) {
+    const int i = (int)blockIdx.x / a.blocks_per_env, blk = (int)blockIdx.x - i * a.blocks_per_env;
+    if (a.state[2 * a.n_envs + i] == 0) return;
+    const uint8_t* src = a.frames + (size_t)i * a.O;
+    uint8_t* dst = a.ring + ((size_t)i * a.L + a.state[i]) * a.O;
+    const int piece = blk * IT + (int)threadIdx.x;
+    if ((a.O & 15) == 0) {
+        if (piece < (a.O >> 4)) st4(reinterpret_cast<float*>(dst) + piece * 4, ld4(reinterpret_cast<const float*>(src) + piece * 4));      // (a 16-byte move)
+    } else {
+        const int b1 = piece * 16 + 16 < a.O ? piece * 16 + 16 : a.O;
+        for (int b = piece * 16; b < b1; ++b) dst[b] = src[b];
+    }
+}
+
+struct ImgActorListArgs {
+    const int32_t* state;
+    int32_t *img_index, *dst, *win;
+    int n_envs, L, reuse;
+};
+// One workgroup: thread t owns a contiguous range of the N L (environment, window row) pairs, the per-thread counts go through an
+// inclusive scan in LDS, every thread then writes its tokens behind those of the threads before it -- window order, no atomics.
+__global__ __launch_bounds__(IT) void img_actor_lists_kernel(ImgActorListArgs a) {
+    __shared__ int32_t sums[IT];
+    const int N = a.n_envs, L = a.L, total = N * L, per = (total + IT - 1) / IT;
+    const int t = (int)threadIdx.x, k0 = t * per < total ? t * per : total, k1 = k0 + per < total ? k0 + per : total;
+    auto token = [&](int k) -> int {                 // ring row of pair k if it has to be encoded, else -1
+        const int i = k / L, r = k - i * L, len = a.state[N + i], head = a.state[i];
+        if (r >= len) return -1;
+        const int slot = (head - (len - 1) + r + L) % L;
+        const bool fresh = a.state[2 * N + i] != 0 && slot == head;
+        if (a.reuse && !fresh && a.state[3 * N + i * L + slot] != 0) return -1;
+        return i * L + slot;
+    };
+    int c = 0;
+    for (int k = k0; k < k1; ++k) c += token(k) >= 0 ? 1 : 0;
+    sums[t] = c;
+    __syncthreads();
+    for (int off = 1; off < IT; off <<= 1) {
+        const int v = t >= off ? sums[t - off] : 0;
+        __syncthreads();
+        sums[t] += v;
+        __syncthreads();
+    }
+    int pos = sums[t] - c;
+    for (int k = k0; k < k1; ++k) {
+        const int row = token(k);
+        if (row >= 0) {
+            a.img_index[pos] = row;
+            a.dst[pos] = row;
+            ++pos;
+        }
+    }
+    for (int i = t; i < N; i += IT) {
+        const int len = a.state[N + i];
+        a.win[i] = (a.state[i] - (len - 1) + L) % L;
+        a.win[N + i] = len;
+    }
+}
+
+struct ImgActorGatherArgs {
+    const float* ering;        // [N][L][D]
+    const int32_t* win;
+    float* xemb;               // [N][n_max][D], window order, zeros behind the live rows
+    int n_envs, L, n_max, D;
+};
+__global__ __launch_bounds__(IT) void img_actor_gather_kernel(ImgActorGatherArgs a) {
+    const int c4n = a.D >> 2;
+    const long long idx = (long long)blockIdx.x * IT + threadIdx.x;
+    if (idx >= (long long)a.n_envs * a.n_max * c4n) return;
+    const int c4 = (int)(idx % c4n), row = (int)(idx / c4n), i = row / a.n_max, r = row - i * a.n_max;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (r < a.win[a.n_envs + i]) v = ld4(a.ering + ((size_t)i * a.L + (a.win[i] + r) % a.L) * a.D + c4 * 4);
+    st4(a.xemb + (size_t)row * a.D + c4 * 4, v);
+}
+
+struct ImgActorQArgs {
+    const float* q;            // [N][n_max][A]
+    const int32_t* win;
+    float* q_last;             // [N][A], pinned host memory
+    int n_envs, n_max, A;
+};
+__global__ __launch_bounds__(IT) void img_actor_qrows_kernel(ImgActorQArgs a) {
+    const int idx = (int)blockIdx.x * IT + (int)threadIdx.x;
+    if (idx >= a.n_envs * a.A) return;
+    const int i = idx / a.A, col = idx - i * a.A;
+    a.q_last[idx] = a.q[((size_t)i * a.n_max + (a.win[a.n_envs + i] - 1)) * a.A + col];
+}
+
+static int g_last_img_actor_tokens = 0;      // tokens the last dtqn_img_actor_forward_batch encoded (tests: dtqn_debug_last_img_actor_tokens)
+
+}  // namespace dtqn
+
+extern "C" int dtqn_debug_last_img_actor_tokens(void) { return g_last_img_actor_tokens; }
+
+extern "C" long long dtqn_img_actor_stage_bytes(const DtqnNet* net, int n_envs) {
+    if (!net || net->img_c <= 0 || n_envs < 1) return 0;
+    return (long long)(img_actor_state_ints(n_envs, net->ctx_len) * sizeof(int32_t)) + (long long)n_envs * net->obs_dim;
+}
+
+extern "C" long long dtqn_img_actor_workspace_floats(const DtqnNet* net, int n_envs) {
+    if (!net || net->img_c <= 0 || !net->tiled || n_envs < 1) return 0;
+    if ((long long)n_envs * net->ctx_len >= (1LL << 24)) return 0;
+    return img_actor_ws(*net, n_envs).total;          // 0: the forward's own workspace query refused the batch
+}
+
+// Embedding reuse on (default) or off (DTQN_IMG_ACTOR_REUSE=0: every live frame is encoded again on every call; A/B and tests, read per call)
+static bool img_actor_reuse() {
+    const char* e = getenv("DTQN_IMG_ACTOR_REUSE");
+    return !(e != nullptr && e[0] == '0');
+}
+
+extern "C" int dtqn_img_actor_forward_batch(const DtqnNet* net, const float* theta, float* wprep, int refresh_prep, const void* stage_host,
+                                            uint8_t* frame_ring, float* emb_ring, int n_envs, float* q_dev, float* q_last_host,
+                                            float* workspace, int train_mode, uint32_t dropout_seed, uint32_t dropout_step, void* stream) {
+    if (!net || net->img_c <= 0 || !net->tiled || net->action_dim != 0 || net->bag_size != 0) return DTQN_ERR_ARG;
+    if (!stage_host || !frame_ring || n_envs < 1) return DTQN_ERR_ARG;
+    const bool push_only = q_last_host == nullptr;       // the frames go to the ring, nothing is encoded or forwarded
+    if (!push_only && (!theta || !wprep || !emb_ring || !q_dev || !workspace)) return DTQN_ERR_ARG;
+    const int N = n_envs, L = net->ctx_len, O = net->obs_dim, D = net->d_model;
+    if ((long long)N * L >= (1LL << 24)) return DTQN_ERR_CONFIG;
+    hipStream_t s = (hipStream_t)stream;
+    // The block is already written: what indexes device memory is checked here, and the token count is taken from the same flags the
+    // list kernel compacts, so the encoder's grid needs no read-back
+    const int32_t* st = static_cast<const int32_t*>(stage_host);
+    const bool reuse = img_actor_reuse();
+    int n_max = 0, tokens = 0;
+    for (int i = 0; i < N; ++i) {
+        const int head = st[i], len = st[N + i], fresh = st[2 * N + i];
+        if (head < 0 || head >= L || len < 1 || len > L || (fresh != 0 && fresh != 1)) return DTQN_ERR_ARG;
+        n_max = len > n_max ? len : n_max;
+        for (int r = 0; r < len; ++r) {
+            const int slot = (head - (len - 1) + r + L) % L;
+            if (!reuse || (fresh && slot == head) || st[3 * N + i * L + slot] == 0) ++tokens;
+        }
+    }
+    if (push_only) tokens = 0;
+    g_last_img_actor_tokens = tokens;
+    const ImgActorWs w = img_actor_ws(*net, N);
+    if (!push_only && w.total <= 0) return DTQN_ERR_CONFIG;
+    {
+        ImgRingArgs a;
+        a.state = st; a.frames = static_cast<const uint8_t*>(stage_host) + img_actor_state_ints(N, L) * sizeof(int32_t);
+        a.ring = frame_ring; a.n_envs = N; a.L = L; a.O = O;
+        a.blocks_per_env = ((O + 15) / 16 + IT - 1) / IT;
+        IMG_LAUNCH(img_ring_push_kernel, N * a.blocks_per_env, 0, s, a);
+    }
+    if (push_only) return DTQN_OK;
+    int32_t* ints = reinterpret_cast<int32_t*>(workspace + w.ints);
+    int32_t *img_index = ints, *dst = ints + (size_t)N * L, *win = ints + 2 * (size_t)N * L;
+    float* xemb = workspace + w.xemb;
+    int rc;
+    if (refresh_prep && (rc = dtqn_img_prep(net, theta, wprep, stream)) != DTQN_OK) return rc;
+    {
+        ImgActorListArgs a;
+        a.state = st; a.img_index = img_index; a.dst = dst; a.win = win; a.n_envs = N; a.L = L; a.reuse = reuse ? 1 : 0;
+        IMG_LAUNCH(img_actor_lists_kernel, 1, 0, s, a);
+    }
+    for (int off = 0; off < tokens; off += kImgActorChunk) {
+        const int n = tokens - off < kImgActorChunk ? tokens - off : kImgActorChunk;
+        if ((rc = dtqn_img_encode(net, theta, wprep, frame_ring, img_index + off, n, workspace + w.act, emb_ring, dst + off, nullptr, nullptr,
+                                  stream)) != DTQN_OK)
+            return rc;
+    }
+    {
+        ImgActorGatherArgs a;
+        a.ering = emb_ring; a.win = win; a.xemb = xemb; a.n_envs = N; a.L = L; a.n_max = n_max; a.D = D;
+        const long long n = (long long)N * n_max * (D >> 2);
+        IMG_LAUNCH(img_actor_gather_kernel, (unsigned)((n + IT - 1) / IT), 0, s, a);
+    }
+    if ((rc = dtqn_forward_tiled_pre(net, theta, xemb, nullptr, N, n_max, q_dev, workspace + w.fwd, train_mode, dropout_seed, dropout_step,
+                                     stream)) != DTQN_OK)
+        return rc;
+    {
+        ImgActorQArgs a;
+        a.q = q_dev; a.win = win; a.q_last = q_last_host; a.n_envs = N; a.n_max = n_max; a.A = net->num_actions;
+        IMG_LAUNCH(img_actor_qrows_kernel, (N * net->num_actions + IT - 1) / IT, 0, s, a);
+    }
+    return DTQN_OK;
+}

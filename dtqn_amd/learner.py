@@ -85,6 +85,7 @@ class TdEngine:
                 raise ValueError(f"batch {self.batch} of this network shape trains on the row-block kernels only and its row-block twin "
                                  "could not be built (dtqn_net_tiled_twin): use a batch inside latency mode or a shape the twin covers")
         self.net = net
+        self.updates = 0              # optimizer launches issued so far: what was derived from theta_pol before the last one is stale
         self._bound_stream = None
         dev = self.device
         nt, nth = net.n_trainable, net.n_theta
@@ -445,8 +446,10 @@ class TdEngine:
             self._check(self.lib.dtqn_td_update_pipelined(self._net_ref, replay.view_ref, self._td_ref, nxt, 1 if have else 0, d, s),
                         "dtqn_td_update_pipelined")
             self._pipe["steps"] += 1
+            self.updates += 1
             return
         self._check(self.lib.dtqn_td_update(self._net_ref, replay.view_ref, self._td_ref, s), "dtqn_td_update")
+        self.updates += 1
         if getattr(self, "_pipe", None) is not None:
             # the one-call update stepped the device's optimizer counter too (host-drawn windows on an engine whose pipeline is
             # enabled): the mirror follows, so the next in-kernel draw and the predicted hard target sync stay keyed by the device's
@@ -500,6 +503,7 @@ class TdEngine:
 
     def clip_adam(self):
         self._check(self.lib.dtqn_td_clip_adam(self._net_ref, self._td_ref, self._stream()), "dtqn_td_clip_adam")
+        self.updates += 1
         if getattr(self, "_pipe", None) is not None:
             self._pipe["steps"] += 1
 

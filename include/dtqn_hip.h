@@ -539,6 +539,33 @@ int dtqn_img_td_lists(const DtqnNet* net, const DtqnReplay* rp, const DtqnTd* td
 int dtqn_forward_tiled_pre(const DtqnNet* net, const float* theta, const float* xemb, const uint8_t* actions, int batch, int n,
                            float* q_out, float* workspace, int train_mode, uint32_t dropout_seed, uint32_t dropout_step, void* stream);
 
+/* Vectorised rollout of image observations: dtqn_actor_forward_batch for image nets (no action embedding, no bag).  The frames of
+ * the N rolling contexts live in frame_ring [N][ctx_len][O] u8 and their embeddings in emb_ring [N][ctx_len][D] f32 (same row
+ * numbering, both caller-owned device memory that only this call writes), so a vector step uploads N frames and encodes only the
+ * frames whose embedding is not current.  stage_host is PINNED, dtqn_img_actor_stage_bytes(net, N) bytes:
+ *   int32 head[N] | len[N] | fresh[N] | valid[N][ctx_len]   (padded to 16 bytes)   |   newest frames [N][O] u8
+ * head_i: ring slot of environment i's newest frame; len_i (1..ctx_len): live rows of its window, window row r being slot
+ * (head_i - (len_i - 1) + r) mod ctx_len; fresh_i: 1 when the block carries a frame for slot head_i (0: nothing new since the last
+ * call); valid[i][s]: emb_ring row (i, s) was written by an earlier call under the parameters now in theta (the caller clears all
+ * of them whenever theta can have changed; a fresh slot counts as not valid whatever its flag says).  The kernels read the block in
+ * place: it may be rewritten once `stream` has drained past this call.  Stages, all on `stream`, nothing allocated: ring push, token
+ * lists (fixed-order compaction; the token count is taken on the host from the same flags, so nothing is read back), dtqn_img_encode
+ * into emb_ring, the window-order gather + row-block forward of n_max = max len_i rows (zeros behind a shorter prefix; causal
+ * attention keeps them out of its live rows), and Q of row len_i - 1 of environment i into the pinned q_last_host[i][num_actions]
+ * (written by a kernel; valid once `stream` has drained).  q_dev: [N][ctx_len][num_actions].  refresh_prep != 0: dtqn_img_prep
+ * (theta -> wprep) runs first -- once per parameter version.  workspace: dtqn_img_actor_workspace_floats(net, N) floats, ZEROED once.
+ * train_mode / dropout_seed / dropout_step as dtqn_actor_forward_batch (dropout acts behind the embeddings, so they stay valid
+ * across a change of mode).  DTQN_IMG_ACTOR_REUSE=0 (tests, A/B; read per call): every live frame is encoded on every call.
+ * q_last_host == NULL: push only -- the fresh frames go to the ring and nothing else runs (a vector step on which every environment
+ * explores); their embeddings stay not valid, so the caller leaves the marks of those slots off. */
+long long dtqn_img_actor_stage_bytes(const DtqnNet* net, int n_envs);
+long long dtqn_img_actor_workspace_floats(const DtqnNet* net, int n_envs);
+int dtqn_img_actor_forward_batch(const DtqnNet* net, const float* theta, float* wprep, int refresh_prep, const void* stage_host,
+                                 uint8_t* frame_ring, float* emb_ring, int n_envs, float* q_dev, float* q_last_host, float* workspace,
+                                 int train_mode, uint32_t dropout_seed, uint32_t dropout_step, void* stream);
+/* Tests: frames the last dtqn_img_actor_forward_batch encoded. */
+int dtqn_debug_last_img_actor_tokens(void);
+
 /* ------------------------------------------------------------------------------------------
  * Differentiable forward (torch autograd through DTQN.forward, dtqn_amd/networks/dtqn.py): DTQN.forward of dtqn.py:158-218 on
  * caller-supplied inputs that keeps what the backward reads, and loss.backward() from an arbitrary dL/dQ.  Row-block networks
