@@ -99,6 +99,8 @@ def load_library(path: str) -> ctypes.CDLL:
         "dtqn_replay_gather_bag": [P(DtqnReplay), vp, vp, vp, i32, i32, u32, vp, vp, vp, vp],
         "dtqn_actor_forward": [P(DtqnNet), vp, vp, vp, i32, vp, vp, vp, i32, u32, u32, vp],
         "dtqn_actor_forward_batch": [P(DtqnNet), vp, vp, vp, i32, i32, vp, vp, vp, i32, u32, u32, vp],
+        "dtqn_actor_greedy_batch": [P(DtqnNet), vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, u32, u32, vp],
+        "dtqn_debug_last_actor_live": [],
         "dtqn_forward_tiled_strided": [P(DtqnNet), vp, vp, vp, i32, i32, i32, vp, vp, vp],
         "dtqn_forward_bag": [P(DtqnNet), vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, u32, u32, vp],
         "dtqn_forward": [P(DtqnNet), vp, vp, vp, i32, i32, vp, vp],
@@ -135,6 +137,7 @@ def load_library(path: str) -> ctypes.CDLL:
         "dtqn_img_actor_stage_bytes": [P(DtqnNet), i32],
         "dtqn_img_actor_workspace_floats": [P(DtqnNet), i32],
         "dtqn_img_actor_forward_batch": [P(DtqnNet), vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, u32, u32, vp],
+        "dtqn_img_actor_greedy_batch": [P(DtqnNet), vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, i32, u32, u32, vp],
         "dtqn_debug_last_img_actor_tokens": [],
         "dtqn_grad_workspace_floats": [P(DtqnNet), i32, i32],
         "dtqn_forward_train": [P(DtqnNet), vp, vp, vp, vp, vp, i32, i32, vp, vp, vp],

@@ -14,9 +14,9 @@ hold exactly what the single-environment loop would have written for that episod
 Pixel observations (agent.image) take the same route with the window kept on the DEVICE: the frames of the N rolling contexts live
 in a ring [N][L][C H W] of uint8 and their embeddings in a second ring [N][L][d_model], so a vector step stages the N newest frames
 only, and `dtqn_img_actor_forward_batch` encodes only the frames whose embedding is not current -- the N new ones while the policy
-parameters stand still, every live one after they moved.  (run.py queues N updates behind every vector step and evaluates and
-prepopulates through the single-environment actor, so there every step re-encodes; the reuse serves callers that drive a VectorActor
-with frozen parameters or with fewer updates than steps.)  A vector step on which every environment explores only pushes its frames.  The host keeps
+parameters stand still, every live one after they moved.  (run.py queues N updates behind every vector step and prepopulates through the
+single-environment actor, so there every step re-encodes; the reuse serves callers with frozen parameters -- `VectorEvaluator` below, what
+`run.py --eval-envs N` evaluates through -- or with fewer updates than steps.)  A vector step on which every environment explores only pushes its frames.  The host keeps
 (slot of the newest frame, live rows, which embeddings are current) per environment and drops the last of these whenever the
 parameters can have changed: an optimizer launch (TdEngine.updates), a host-side write to the flat buffer or to one of the
 Parameters that view it (their torch `_version`: load_state_dict, a checkpoint restore, an in-place op), a re-bound buffer.  The target network has its own
@@ -27,6 +27,7 @@ policy network's `alpha` / `attn_weights` are those of its last module forward (
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 from typing import List, Sequence
 
@@ -159,7 +160,37 @@ class VectorActor:
         """Stage the newest frame of every environment and launch the batched image actor forward (no synchronisation).
         push_only: a vector step on which every environment explores -- the frames go to the ring, nothing is encoded or forwarded
         (their embeddings stay marked as missing and are made by the next full launch)."""
-        a, eng, L = self.agent, self.agent.engine, self.L
+        a, eng = self.agent, self.agent.engine
+        refresh = self._stage_image()
+        p = self._p
+        if push_only:
+            self._prep_due = self._prep_due or refresh
+            rc = eng.lib.dtqn_img_actor_forward_batch(eng._actor_net_ref, None, None, 0, p[1], p[2], None, self.n, None, None, None, 0, 0, 0, eng._stream())
+        else:
+            a._actor_calls += 1
+            rc = eng.lib.dtqn_img_actor_forward_batch(eng._actor_net_ref, a._theta_p, p[0], 1 if (refresh or self._prep_due) else 0, p[1], p[2], p[3],
+                                                      self.n, p[4], p[5], p[6], 1 if a.train_mode.name == "TRAIN" else 0,
+                                                      eng.td.dropout_seed ^ 0xAC70, a._actor_calls & 0xFFFFFFFF, eng._stream())
+        if rc != 0:
+            raise RuntimeError(f"dtqn_img_actor_forward_batch failed with DTQN status {rc}")
+        if not push_only:
+            self._image_launched()
+        if self._ev is not None:
+            self._ev.record(a._main_stream)
+        self._inflight = True
+
+    def _image_launched(self, live=None) -> None:
+        """Behind a full launch every live row of every (live) environment holds a current embedding."""
+        self._prep_due = False
+        for i, ctx in enumerate(self.contexts):
+            if live is None or live[i]:
+                self._valid[i, :min(self.L, ctx.timestep + 1)] = 1
+
+    def _stage_image(self, live=None) -> bool:
+        """Fill the pinned block of an image launch: the newest frame of every environment that has one the ring has not seen, window
+        heads and lengths, the valid marks.  live: per environment, False = idle (length 0: dtqn_img_actor_greedy_batch); None = all.
+        Returns whether the parameters moved since the last launch (all marks were dropped, the encoder's weights are due)."""
+        eng, L = self.agent.engine, self.L
         if self._inflight and self._ev is not None:
             self._ev.synchronize()              # the kernels of the last launch read the pinned block in place
         # (a Parameter that was re-pointed at a moved flat buffer keeps a version counter of its own: both are asked)
@@ -169,6 +200,9 @@ class VectorActor:
             self._valid[:] = 0
             self._param_version = version
         for i, ctx in enumerate(self.contexts):
+            if live is not None and not live[i]:
+                self._head_np[i], self._len_np[i], self._fresh_np[i] = 0, 0, 0
+                continue
             t = ctx.timestep
             n, head = min(L, t + 1), t % L
             fresh = 0
@@ -182,24 +216,7 @@ class VectorActor:
                 fresh = 1
             self._head_np[i], self._len_np[i], self._fresh_np[i] = head, n, fresh
         self._valid_np[:] = self._valid
-        p = self._p
-        if push_only:
-            self._prep_due = self._prep_due or refresh
-            rc = eng.lib.dtqn_img_actor_forward_batch(eng._actor_net_ref, None, None, 0, p[1], p[2], None, self.n, None, None, None, 0, 0, 0, eng._stream())
-        else:
-            a._actor_calls += 1
-            rc = eng.lib.dtqn_img_actor_forward_batch(eng._actor_net_ref, a._theta_p, p[0], 1 if (refresh or self._prep_due) else 0, p[1], p[2], p[3],
-                                                      self.n, p[4], p[5], p[6], 1 if a.train_mode.name == "TRAIN" else 0,
-                                                      eng.td.dropout_seed ^ 0xAC70, a._actor_calls & 0xFFFFFFFF, eng._stream())
-        if rc != 0:
-            raise RuntimeError(f"dtqn_img_actor_forward_batch failed with DTQN status {rc}")
-        if not push_only:
-            self._prep_due = False
-            for i, ctx in enumerate(self.contexts):        # behind this launch every live row holds a current embedding
-                self._valid[i, :min(L, ctx.timestep + 1)] = 1
-        if self._ev is not None:
-            self._ev.record(a._main_stream)
-        self._inflight = True
+        return refresh
 
     def _launch_q(self) -> None:
         """Stage all N contexts and launch the batched actor forward on the learner's stream (no synchronisation)."""
@@ -207,33 +224,7 @@ class VectorActor:
         if self.image is not None:
             return self._launch_q_image()
         if self.bags is not None:
-            # bag networks: the module forward with the N bags (dtqn_forward_bag); every sequence runs the longest prefix, the
-            # rows behind a shorter one cannot reach its last live row (causal), its own bag attends row by row
-            lens = [min(c.max_length, c.timestep + 1) for c in self.contexts]
-            groups = [list(range(self.n))]
-            if a.policy_network.net.action_dim > 0 and max(lens) > 1 and min(lens) == 1:
-                # a ONE-row sequence keeps its action embedding un-rolled (dtqn.py:187-191: `if history_len > 1`); run next to longer
-                # prefixes it would be rolled and zeroed, so the fresh episodes of this vector step get a forward of their own
-                groups = [[i for i in range(self.n) if lens[i] > 1], [i for i in range(self.n) if lens[i] == 1]]
-            q_rows = None
-            for idx in groups:
-                n_max = max(lens[i] for i in idx)
-                obs = np.stack([self.contexts[i].obs[:n_max] for i in idx])
-                act = np.stack([self.contexts[i].action[:n_max] for i in idx])
-                q = a._bag_forward(obs, act, np.stack([self.bags[i].obss for i in idx]), np.stack([self.bags[i].actions for i in idx]))
-                rows = torch.as_tensor(np.asarray([lens[i] for i in idx]) - 1, device=q.device)
-                last = q[torch.arange(len(idx), device=q.device), rows]           # the last live row of every sequence
-                if q_rows is None:
-                    q_rows = torch.empty(self.n, self.A, dtype=q.dtype, device=q.device)
-                q_rows[torch.as_tensor(idx, device=q.device)] = last
-            # -> pinned memory with one asynchronous copy, and an event right behind it: updates queued after this point
-            # (step_all's `between`) no longer stand between the host and its Q-values
-            if self._ev is not None:
-                self._q_h.copy_(q_rows, non_blocking=True)
-                self._ev.record(torch.cuda.current_stream(a.device))
-            else:
-                self._q_h.copy_(q_rows)
-            return
+            return self._launch_q_bag(list(range(self.n)))
         n_max = 1
         for i, ctx in enumerate(self.contexts):
             n = min(ctx.max_length, ctx.timestep + 1)
@@ -250,6 +241,36 @@ class VectorActor:
             raise RuntimeError(f"dtqn_actor_forward_batch failed with DTQN status {rc}")
         if self._ev is not None:
             self._ev.record(a._main_stream)
+
+    def _launch_q_bag(self, envs: List[int]) -> None:
+        """Bag networks: the module forward with the bags of `envs` (dtqn_forward_bag; all N in a rollout, the environments that still play
+        in an evaluation); every sequence runs the longest prefix, the rows behind a shorter one cannot reach its last live row (causal),
+        its own bag attends row by row.  The Q rows of the other environments come back as zeros."""
+        a = self.agent
+        lens = {i: min(self.contexts[i].max_length, self.contexts[i].timestep + 1) for i in envs}
+        groups = [list(envs)]
+        if a.policy_network.net.action_dim > 0 and max(lens.values()) > 1 and min(lens.values()) == 1:
+            # a ONE-row sequence keeps its action embedding un-rolled (dtqn.py:187-191: `if history_len > 1`); run next to longer
+            # prefixes it would be rolled and zeroed, so the fresh episodes of this vector step get a forward of their own
+            groups = [[i for i in envs if lens[i] > 1], [i for i in envs if lens[i] == 1]]
+        q_rows = None
+        for idx in groups:
+            n_max = max(lens[i] for i in idx)
+            obs = np.stack([self.contexts[i].obs[:n_max] for i in idx])
+            act = np.stack([self.contexts[i].action[:n_max] for i in idx])
+            q = a._bag_forward(obs, act, np.stack([self.bags[i].obss for i in idx]), np.stack([self.bags[i].actions for i in idx]))
+            rows = torch.as_tensor(np.asarray([lens[i] for i in idx]) - 1, device=q.device)
+            last = q[torch.arange(len(idx), device=q.device), rows]           # the last live row of every sequence
+            if q_rows is None:
+                q_rows = (torch.empty if len(envs) == self.n else torch.zeros)(self.n, self.A, dtype=q.dtype, device=q.device)
+            q_rows[torch.as_tensor(idx, device=q.device)] = last
+        # -> pinned memory with one asynchronous copy, and an event right behind it: updates queued after this point
+        # (step_all's `between`) no longer stand between the host and its Q-values
+        if self._ev is not None:
+            self._q_h.copy_(q_rows, non_blocking=True)
+            self._ev.record(torch.cuda.current_stream(a.device))
+        else:
+            self._q_h.copy_(q_rows)
 
     def _wait_q(self) -> np.ndarray:
         if self._ev is not None:
@@ -317,3 +338,124 @@ class VectorActor:
         for t, (obs, a, r, d) in enumerate(ep[1:]):
             rb.store(obs, a, r, d, t + 1)
         rb.flush()
+
+
+@contextlib.contextmanager
+def _private_rng(seed: int):
+    """RNG.rng replaced by a generator of the caller's own for the duration: what runs inside draws nothing from the global stream."""
+    keep, RNG.rng = RNG.rng, np.random.Generator(np.random.PCG64(seed))
+    try:
+        yield
+    finally:
+        RNG.rng = keep
+
+
+class VectorEvaluator(VectorActor):
+    """Greedy evaluation (reference run.py:187-243) of N environments at once: one batched launch per vector step, the arg-max taken on
+    the device (`dtqn_actor_greedy_batch`, `dtqn_img_actor_greedy_batch`; bag networks: the module forward over the environments that
+    still play).  The evaluator owns its N environments and N contexts (and bags): the agent's train and eval contexts, its replay
+    and `RNG.rng` are not touched, the network runs in eval mode (no dropout) as under `eval_on()`.
+
+    `evaluate(episodes)` deals the episodes out in order -- environment i plays episodes i, i + N, ... -- and an environment with no
+    episode left goes idle: it is staged with length 0, takes no sequence of the forward and, with pixel observations, pushes no frame.
+    The parameters stand still for a whole evaluation, so the embedding ring's valid marks are dropped once at its start (and again only
+    if the parameter watch of `VectorActor` sees them move): every frame is encoded exactly once."""
+
+    def __init__(self, agent, envs: Sequence, ref_quirks: bool = False):
+        with _private_rng(0):
+            super().__init__(agent, envs, ref_quirks=ref_quirks)
+        pin = (lambda t: t.pin_memory()) if agent.device.type == "cuda" else (lambda t: t)
+        self._greedy_h = pin(torch.full((self.n,), -1, dtype=torch.int32))         # the actions, written by the greedy kernel
+        self._greedy_np = self._greedy_h.numpy()
+        self._greedy_p = ctypes.c_void_p(self._greedy_h.data_ptr())
+        self.live = np.zeros(self.n, dtype=bool)
+
+    def _greedy_actions(self) -> np.ndarray:
+        """The greedy action of every live environment (int per environment; -1 for an idle one): one launch, awaited."""
+        a, eng, live = self.agent, self.agent.engine, self.live
+        if self.bags is not None:
+            envs = [i for i in range(self.n) if live[i]]
+            self._launch_q_bag(envs)
+            q = self._wait_q()
+            self._greedy_np[:] = -1
+            self._greedy_np[envs] = np.argmax(q[envs], axis=1)          # first max, like torch.argmax
+            return self._greedy_np
+        if self.image is not None:
+            refresh = self._stage_image(live)
+            p = self._p
+            rc = eng.lib.dtqn_img_actor_greedy_batch(eng._actor_net_ref, a._theta_p, p[0], 1 if (refresh or self._prep_due) else 0, p[1], p[2],
+                                                     p[3], self.n, p[4], p[5], self._greedy_p, p[6], 0, 0, 0, eng._stream())
+            if rc != 0:
+                raise RuntimeError(f"dtqn_img_actor_greedy_batch failed with DTQN status {rc}")
+            self._image_launched(live)
+            self._inflight = True
+        else:
+            n_max = 0
+            for i, ctx in enumerate(self.contexts):
+                n = min(ctx.max_length, ctx.timestep + 1) if live[i] else 0
+                if n > 0:
+                    self._obs_np[i, :n] = ctx.obs[:n]
+                    self._act_np[i, :n] = ctx.action[:n, 0]
+                self._len_np[i] = n
+                n_max = max(n_max, n)
+            rc = eng.lib.dtqn_actor_greedy_batch(eng._actor_net_ref, a._theta_p, self._p[0], self._p[1], self.n, n_max, self._p[2], self._p[3],
+                                                 self._greedy_p, self._ws_p, 0, 0, 0, eng._stream())
+            if rc == B.DEFINES["DTQN_ERR_ARG"]:
+                raise AssertionError("Cannot forward, history is longer than expected.")   # dtqn.py:170-173
+            if rc != 0:
+                raise RuntimeError(f"dtqn_actor_greedy_batch failed with DTQN status {rc}")
+        if self._ev is not None:
+            self._ev.record(a._main_stream)
+        self._wait_q()
+        return self._greedy_np
+
+    def _begin_episode(self, i: int, episode: int) -> None:
+        # a context fills the action rows behind its prefix from RNG.rng (utils/context.py): here from a stream of the episode's own,
+        # so the exploration stream stands still and an episode does not depend on which environment plays it
+        with _private_rng(episode):
+            self._reset(i)                 # environment, context, bag, ring marks; episodes[i] = [the first observation]
+        self.live[i] = True
+
+    @torch.no_grad()
+    def evaluate(self, episodes: int):
+        """(success rate, mean return, mean episode length) over `episodes` greedy episodes, by the formulas of run.evaluate: success
+        is info["is_success"] or a positive return, the length is the context's timestep when the episode ends."""
+        agent, N = self.agent, self.n
+        agent.eval_on()
+        if self.image is not None:
+            self._valid[:] = 0
+            self._param_version = None     # the first launch refreshes the encoder's transposed weights
+        episode = np.full(N, -1, dtype=np.int64)          # the episode each environment is playing
+        results = [None] * episodes                       # (return, length, success) in episode order
+        self.live[:] = False
+        for i in range(min(N, episodes)):
+            episode[i] = i
+            self._begin_episode(i, i)
+        while self.live.any():
+            actions = self._greedy_actions()
+            for i in range(N):
+                if not self.live[i]:
+                    continue
+                act = int(actions[i])
+                obs, reward, done, info = self.envs[i].step(act)
+                evicted_obs, evicted_action = self.contexts[i].add_transition(obs, act, reward, done)
+                if self.bags is not None and evicted_obs is not None:
+                    agent._bag_insert(self.bags[i], self.contexts[i], evicted_obs, evicted_action)
+                self.episodes[i] = [np.array(obs, copy=True)]         # the newest frame (what the image staging reads)
+                self.returns[i] += reward
+                if done:
+                    ret = float(self.returns[i])
+                    results[episode[i]] = (ret, self.contexts[i].timestep, int(info.get("is_success", False) or ret > 0))
+                    episode[i] += N
+                    if episode[i] < episodes:
+                        self._begin_episode(i, int(episode[i]))
+                    else:
+                        self.live[i] = False
+        agent.eval_off()
+        n = max(episodes, 1)
+        returns = successes = steps = 0
+        for ret, length, ok in results:
+            returns += ret
+            steps += length
+            successes += ok
+        return successes / n, returns / n, steps / n

@@ -135,6 +135,9 @@ int forward_infer(const DtqnNet* net, const float* theta, const float* obs, cons
                   uint32_t drop_seed, uint32_t drop_step, int train_mode);
 int tiled_forward_actor(const DtqnNet* net, const float* theta, const float* obs, const uint8_t* actions, int batch, int n, int in_rows,
                         float* q_out, float* workspace, int train_mode, uint32_t drop_seed, uint32_t drop_step, hipStream_t stream, const int32_t* lens = nullptr);
+int actor_compact(const DtqnNet* net, const void* ctx_host, void* ctx_dev, int n_envs, int n_max, hipStream_t stream);
+int actor_greedy_rows(const int32_t* lens, const float* q, float* q_last, int32_t* action, int n_envs, int n_max, int A, hipStream_t stream);
+void set_last_actor_live(int live);
 }
 extern "C" int dtqn_forward_tiled_strided(const DtqnNet* net, const float* theta, const float* obs, const uint8_t* actions,
                                           int batch, int n, int in_rows, float* q_out, float* workspace, void* stream);
@@ -173,6 +176,35 @@ extern "C" int dtqn_actor_forward(const DtqnNet* net, const float* theta, const 
     return DTQN_OK;
 }
 
+// The packed block of the batched actor entry points (pinned host copy and device copy alike), and the forward both run on it
+struct ActorBlock {
+    const float* obs;
+    const uint8_t* actions;
+    const int32_t* lens;
+};
+static ActorBlock actor_block(const DtqnNet* net, void* base, int n_envs) {
+    const size_t obs_bytes = sizeof(float) * (size_t)n_envs * net->ctx_len * net->obs_dim;
+    const size_t act_bytes = (((size_t)n_envs * net->ctx_len) + 3) & ~(size_t)3;       // keeps the int32 block 4-byte aligned
+    const uint8_t* p = static_cast<const uint8_t*>(base);
+    return ActorBlock{static_cast<const float*>(base), p + obs_bytes, reinterpret_cast<const int32_t*>(p + obs_bytes + act_bytes)};
+}
+// batch: sequences in the block (its first `batch` slots); ws_envs: the batch `workspace` was laid out for (>= batch).  Row-block nets
+// leave Q in q_dev only; the whole-sequence kernels also write row len_s - 1 of sequence s to q_last_host[s] when that is given.
+static int actor_batch_forward(const DtqnNet* net, const float* theta, const ActorBlock& b, int batch, int ws_envs, int n_max, float* q_dev,
+                               float* q_last_host, float* workspace, int train_mode, uint32_t dropout_seed, uint32_t dropout_step,
+                               void* stream) {
+    const int L = net->ctx_len;
+    if (net->tiled)
+        return dtqn::tiled_forward_actor(net, theta, b.obs, b.actions, batch, n_max, L, q_dev, workspace, train_mode, dropout_seed,
+                                         dropout_step, (hipStream_t)stream, b.lens);
+    // few actors: two workgroups per sequence once the longest prefix reaches the upper half (workspace = hand-over tiles | flags)
+    const bool split = workspace != nullptr && n_max > net->lp / 2 && dtqn_td_row_split(net, batch) >= 2;
+    float* xch = split ? workspace : nullptr;
+    int32_t* xflags = split ? reinterpret_cast<int32_t*>(workspace + dtqn_td_xch_floats(net, ws_envs)) : nullptr;
+    return dtqn::forward_infer(net, theta, b.obs, b.actions, batch, n_max, q_dev, q_last_host, stream, xch, xflags, b.lens, L, dropout_seed,
+                               dropout_step, train_mode);
+}
+
 // The same for N actors at once (vectorised rollout: N host environments per learner, one launch per vector step).
 // ctx_host is PINNED: [N][ctx_len * obs_dim f32] observations | [N][ctx_len u8] actions | [N] int32 live rows n_i (1..ctx_len),
 // copied to ctx_dev (same layout) in ONE hipMemcpyAsync.  Every sequence runs n_max = max n_i rows -- attention is causal, so
@@ -195,25 +227,48 @@ extern "C" int dtqn_actor_forward_batch(const DtqnNet* net, const float* theta, 
     for (int i = 0; i < n_envs; ++i)
         if (lens_h[i] < 1 || lens_h[i] > n_max) return DTQN_ERR_ARG;
     if (hipMemcpyAsync(ctx_dev, ctx_host, total, hipMemcpyHostToDevice, s) != hipSuccess) return DTQN_ERR_LAUNCH;
-    const float* obs = static_cast<const float*>(ctx_dev);
-    const uint8_t* actions = static_cast<const uint8_t*>(ctx_dev) + obs_bytes;
-    const int32_t* lens = reinterpret_cast<const int32_t*>(static_cast<const uint8_t*>(ctx_dev) + obs_bytes + act_bytes);
-    if (net->tiled) {
-        // row-block tiled nets: the forward leaves Q in q_dev; the last rows come back with one small copy per actor
-        const int rc = dtqn::tiled_forward_actor(net, theta, obs, actions, n_envs, n_max, L, q_dev, workspace, train_mode, dropout_seed,
-                                                 dropout_step, (hipStream_t)stream, lens);
-        if (rc != DTQN_OK) return rc;
-        for (int i = 0; i < n_envs; ++i)
-            if (hipMemcpyAsync(q_last_host + (size_t)i * net->num_actions, q_dev + ((size_t)i * n_max + (lens_h[i] - 1)) * net->num_actions,
-                               sizeof(float) * net->num_actions, hipMemcpyDeviceToHost, s) != hipSuccess)
-                return DTQN_ERR_LAUNCH;
+    const ActorBlock b = actor_block(net, ctx_dev, n_envs);
+    const int rc = actor_batch_forward(net, theta, b, n_envs, n_envs, n_max, q_dev, q_last_host, workspace, train_mode, dropout_seed,
+                                       dropout_step, stream);
+    if (rc != DTQN_OK || !net->tiled) return rc;
+    // row-block tiled nets: the forward leaves Q in q_dev; the last rows come back with one small copy per actor
+    for (int i = 0; i < n_envs; ++i)
+        if (hipMemcpyAsync(q_last_host + (size_t)i * net->num_actions, q_dev + ((size_t)i * n_max + (lens_h[i] - 1)) * net->num_actions,
+                           sizeof(float) * net->num_actions, hipMemcpyDeviceToHost, s) != hipSuccess)
+            return DTQN_ERR_LAUNCH;
+    return DTQN_OK;
+}
+
+// Greedy evaluation on the same block (run.py:187-243 plays its evaluation episodes one forward per step): len_i == 0 marks
+// environment i as idle.  The len block the caller staged is the one source of which environments are live: the host counts them
+// here, the compaction kernel reads the same numbers in place, nothing is read back.  Compaction (pinned block -> sequences
+// 0 .. live - 1 of ctx_dev, environment order), the forward of dtqn_actor_forward_batch over `live` sequences, then one kernel that
+// writes Q of row len_i - 1 and its arg-max for every environment (-1 for an idle one) into pinned memory.
+extern "C" int dtqn_actor_greedy_batch(const DtqnNet* net, const float* theta, const void* ctx_host, void* ctx_dev, int n_envs,
+                                       int n_max, float* q_dev, float* q_last_host, int32_t* action_host, float* workspace,
+                                       int train_mode, uint32_t dropout_seed, uint32_t dropout_step, void* stream) {
+    if (!net || !theta || !ctx_host || !ctx_dev || !q_dev || !q_last_host || !action_host || n_envs < 1) return DTQN_ERR_ARG;
+    if (n_max < 0 || n_max > net->ctx_len) return DTQN_ERR_ARG;                 // dtqn.py:170-173
+    const ActorBlock h = actor_block(net, const_cast<void*>(ctx_host), n_envs);
+    int live = 0;
+    for (int i = 0; i < n_envs; ++i) {
+        if (h.lens[i] < 0 || h.lens[i] > n_max) return DTQN_ERR_ARG;
+        live += h.lens[i] > 0 ? 1 : 0;
+    }
+    dtqn::set_last_actor_live(live);
+    if (live == 0) {                      // nothing to launch: the answer is host memory, written here
+        for (int i = 0; i < n_envs; ++i) action_host[i] = -1;
         return DTQN_OK;
     }
-    // few actors: two workgroups per sequence once the longest prefix reaches the upper half (workspace = hand-over tiles | flags)
-    const bool split = workspace != nullptr && n_max > net->lp / 2 && dtqn_td_row_split(net, n_envs) >= 2;
-    float* xch = split ? workspace : nullptr;
-    int32_t* xflags = split ? reinterpret_cast<int32_t*>(workspace + dtqn_td_xch_floats(net, n_envs)) : nullptr;
-    return dtqn::forward_infer(net, theta, obs, actions, n_envs, n_max, q_dev, q_last_host, stream, xch, xflags, lens, L, dropout_seed, dropout_step, train_mode);
+    hipStream_t s = (hipStream_t)stream;
+    int rc;
+    if ((rc = dtqn::actor_compact(net, ctx_host, ctx_dev, n_envs, n_max, s)) != DTQN_OK) return rc;
+    const ActorBlock b = actor_block(net, ctx_dev, n_envs);
+    // (the kernel's own pinned Q rows would land at the sequence's index, not the environment's: the rows are taken from q_dev)
+    if ((rc = actor_batch_forward(net, theta, b, live, n_envs, n_max, q_dev, nullptr, workspace, train_mode, dropout_seed, dropout_step,
+                                  stream)) != DTQN_OK)
+        return rc;
+    return dtqn::actor_greedy_rows(h.lens, q_dev, q_last_host, action_host, n_envs, n_max, net->num_actions, s);
 }
 
 // The differentiable forward without dropout (the function the no-grad forward computes): the _drop entry points with the masks off.

@@ -17,6 +17,7 @@
 //     back in the reference layout.
 // Bound: f32 MFMA (2 * 9 * Cin * Cout FLOP per output pixel; 787 MFLOP per 144 x 144 token forward).
 #include "dtqn_device.hpp"
+#include "dtqn_actor.hpp"
 #include "dtqn_frag16.hpp"
 
 namespace dtqn {
@@ -956,7 +957,7 @@ static inline ImgActorWs img_actor_ws(const DtqnNet& net, int n_envs) {
     }
     w.xemb = up4(fwd);
     w.ints = w.xemb + up4(rows * net.d_model);
-    w.act = w.ints + up4(2 * rows + 2LL * n_envs);                // img_index | dst | win0[N] | len[N]
+    w.act = w.ints + up4(2 * rows + 3LL * n_envs);                // img_index | dst | win0[N] | len[N] | live[N]
     w.total = w.act + up4(dtqn_img_act_floats(&net, (int)(rows < kImgActorChunk ? rows : kImgActorChunk)));
     return w;
 }
@@ -970,7 +971,7 @@ struct ImgRingArgs {
 // 16 bytes per thread; frames whose size is no multiple of 16 go byte by byte (their rows are not 16-byte aligned in either array)
 __global__ __launch_bounds__(IT) void img_ring_push_kernel(ImgRingArgs a) {
     const int i = (int)blockIdx.x / a.blocks_per_env, blk = (int)blockIdx.x - i * a.blocks_per_env;
-    if (a.state[2 * a.n_envs + i] == 0) return;
+    if (a.state[2 * a.n_envs + i] == 0 || a.state[a.n_envs + i] == 0) return;      // nothing new, or an idle environment (greedy evaluation)
     const uint8_t* src = a.frames + (size_t)i * a.O;
     uint8_t* dst = a.ring + ((size_t)i * a.L + a.state[i]) * a.O;
     const int piece = blk * IT + (int)threadIdx.x;
@@ -985,6 +986,7 @@ __global__ __launch_bounds__(IT) void img_ring_push_kernel(ImgRingArgs a) {
 struct ImgActorListArgs {
     const int32_t* state;
     int32_t *img_index, *dst, *win;
+    int32_t* live;             // greedy evaluation: environments with len > 0, in order (the sequences of the forward); nullptr: every one is
     int n_envs, L, reuse;
 };
 // One workgroup: thread t owns a contiguous range of the N L (environment, window row) pairs, the per-thread counts go through an
@@ -1003,15 +1005,7 @@ __global__ __launch_bounds__(IT) void img_actor_lists_kernel(ImgActorListArgs a)
     };
     int c = 0;
     for (int k = k0; k < k1; ++k) c += token(k) >= 0 ? 1 : 0;
-    sums[t] = c;
-    __syncthreads();
-    for (int off = 1; off < IT; off <<= 1) {
-        const int v = t >= off ? sums[t - off] : 0;
-        __syncthreads();
-        sums[t] += v;
-        __syncthreads();
-    }
-    int pos = sums[t] - c;
+    int pos = block_scan_exclusive<IT>(sums, t, c);
     for (int k = k0; k < k1; ++k) {
         const int row = token(k);
         if (row >= 0) {
@@ -1025,19 +1019,29 @@ __global__ __launch_bounds__(IT) void img_actor_lists_kernel(ImgActorListArgs a)
         a.win[i] = (a.state[i] - (len - 1) + L) % L;
         a.win[N + i] = len;
     }
+    if (a.live != nullptr) {                         // the same compaction over the environments
+        const int pe = (N + IT - 1) / IT, i0 = t * pe < N ? t * pe : N, i1 = i0 + pe < N ? i0 + pe : N;
+        int cl = 0;
+        for (int i = i0; i < i1; ++i) cl += a.state[N + i] > 0 ? 1 : 0;
+        int j = block_scan_exclusive<IT>(sums, t, cl);
+        for (int i = i0; i < i1; ++i)
+            if (a.state[N + i] > 0) a.live[j++] = i;
+    }
 }
 
 struct ImgActorGatherArgs {
     const float* ering;        // [N][L][D]
     const int32_t* win;
-    float* xemb;               // [N][n_max][D], window order, zeros behind the live rows
-    int n_envs, L, n_max, D;
+    const int32_t* live;       // environment of sequence s (greedy evaluation), or nullptr: s itself
+    float* xemb;               // [n_seq][n_max][D], window order, zeros behind the live rows
+    int n_envs, n_seq, L, n_max, D;
 };
 __global__ __launch_bounds__(IT) void img_actor_gather_kernel(ImgActorGatherArgs a) {
     const int c4n = a.D >> 2;
     const long long idx = (long long)blockIdx.x * IT + threadIdx.x;
-    if (idx >= (long long)a.n_envs * a.n_max * c4n) return;
-    const int c4 = (int)(idx % c4n), row = (int)(idx / c4n), i = row / a.n_max, r = row - i * a.n_max;
+    if (idx >= (long long)a.n_seq * a.n_max * c4n) return;
+    const int c4 = (int)(idx % c4n), row = (int)(idx / c4n), sq = row / a.n_max, r = row - sq * a.n_max;
+    const int i = a.live != nullptr ? a.live[sq] : sq;
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
     if (r < a.win[a.n_envs + i]) v = ld4(a.ering + ((size_t)i * a.L + (a.win[i] + r) % a.L) * a.D + c4 * 4);
     st4(a.xemb + (size_t)row * a.D + c4 * 4, v);
@@ -1079,9 +1083,12 @@ static bool img_actor_reuse() {
     return !(e != nullptr && e[0] == '0');
 }
 
-extern "C" int dtqn_img_actor_forward_batch(const DtqnNet* net, const float* theta, float* wprep, int refresh_prep, const void* stage_host,
-                                            uint8_t* frame_ring, float* emb_ring, int n_envs, float* q_dev, float* q_last_host,
-                                            float* workspace, int train_mode, uint32_t dropout_seed, uint32_t dropout_step, void* stream) {
+// action_host != nullptr: greedy evaluation (dtqn_img_actor_greedy_batch) -- len_i == 0 marks an idle environment, which pushes no
+// frame, contributes no token and occupies no sequence of the forward; the arg-max of every live Q row goes to action_host
+static int img_actor_run(const DtqnNet* net, const float* theta, float* wprep, int refresh_prep, const void* stage_host, uint8_t* frame_ring,
+                         float* emb_ring, int n_envs, float* q_dev, float* q_last_host, int32_t* action_host, float* workspace, int train_mode,
+                         uint32_t dropout_seed, uint32_t dropout_step, void* stream) {
+    const bool greedy = action_host != nullptr;
     if (!net || net->img_c <= 0 || !net->tiled || net->action_dim != 0 || net->bag_size != 0) return DTQN_ERR_ARG;
     if (!stage_host || !frame_ring || n_envs < 1) return DTQN_ERR_ARG;
     const bool push_only = q_last_host == nullptr;       // the frames go to the ring, nothing is encoded or forwarded
@@ -1093,11 +1100,12 @@ extern "C" int dtqn_img_actor_forward_batch(const DtqnNet* net, const float* the
     // list kernel compacts, so the encoder's grid needs no read-back
     const int32_t* st = static_cast<const int32_t*>(stage_host);
     const bool reuse = img_actor_reuse();
-    int n_max = 0, tokens = 0;
+    int n_max = 0, tokens = 0, n_seq = 0;
     for (int i = 0; i < N; ++i) {
         const int head = st[i], len = st[N + i], fresh = st[2 * N + i];
-        if (head < 0 || head >= L || len < 1 || len > L || (fresh != 0 && fresh != 1)) return DTQN_ERR_ARG;
+        if (head < 0 || head >= L || len < (greedy ? 0 : 1) || len > L || (fresh != 0 && fresh != 1)) return DTQN_ERR_ARG;
         n_max = len > n_max ? len : n_max;
+        n_seq += len > 0 ? 1 : 0;
         for (int r = 0; r < len; ++r) {
             const int slot = (head - (len - 1) + r + L) % L;
             if (!reuse || (fresh && slot == head) || st[3 * N + i * L + slot] == 0) ++tokens;
@@ -1105,6 +1113,13 @@ extern "C" int dtqn_img_actor_forward_batch(const DtqnNet* net, const float* the
     }
     if (push_only) tokens = 0;
     g_last_img_actor_tokens = tokens;
+    if (greedy) {
+        set_last_actor_live(n_seq);
+        if (n_seq == 0) {                 // nothing to launch: the answer is host memory, written here
+            for (int i = 0; i < N; ++i) action_host[i] = -1;
+            return DTQN_OK;
+        }
+    }
     const ImgActorWs w = img_actor_ws(*net, N);
     if (!push_only && w.total <= 0) return DTQN_ERR_CONFIG;
     {
@@ -1116,13 +1131,13 @@ extern "C" int dtqn_img_actor_forward_batch(const DtqnNet* net, const float* the
     }
     if (push_only) return DTQN_OK;
     int32_t* ints = reinterpret_cast<int32_t*>(workspace + w.ints);
-    int32_t *img_index = ints, *dst = ints + (size_t)N * L, *win = ints + 2 * (size_t)N * L;
+    int32_t *img_index = ints, *dst = ints + (size_t)N * L, *win = ints + 2 * (size_t)N * L, *live = greedy ? win + 2 * (size_t)N : nullptr;
     float* xemb = workspace + w.xemb;
     int rc;
     if (refresh_prep && (rc = dtqn_img_prep(net, theta, wprep, stream)) != DTQN_OK) return rc;
     {
         ImgActorListArgs a;
-        a.state = st; a.img_index = img_index; a.dst = dst; a.win = win; a.n_envs = N; a.L = L; a.reuse = reuse ? 1 : 0;
+        a.state = st; a.img_index = img_index; a.dst = dst; a.win = win; a.live = live; a.n_envs = N; a.L = L; a.reuse = reuse ? 1 : 0;
         IMG_LAUNCH(img_actor_lists_kernel, 1, 0, s, a);
     }
     for (int off = 0; off < tokens; off += kImgActorChunk) {
@@ -1133,17 +1148,34 @@ extern "C" int dtqn_img_actor_forward_batch(const DtqnNet* net, const float* the
     }
     {
         ImgActorGatherArgs a;
-        a.ering = emb_ring; a.win = win; a.xemb = xemb; a.n_envs = N; a.L = L; a.n_max = n_max; a.D = D;
-        const long long n = (long long)N * n_max * (D >> 2);
+        a.ering = emb_ring; a.win = win; a.live = live; a.xemb = xemb; a.n_envs = N; a.n_seq = n_seq; a.L = L; a.n_max = n_max; a.D = D;
+        const long long n = (long long)n_seq * n_max * (D >> 2);
         IMG_LAUNCH(img_actor_gather_kernel, (unsigned)((n + IT - 1) / IT), 0, s, a);
     }
-    if ((rc = dtqn_forward_tiled_pre(net, theta, xemb, nullptr, N, n_max, q_dev, workspace + w.fwd, train_mode, dropout_seed, dropout_step,
+    if ((rc = dtqn_forward_tiled_pre(net, theta, xemb, nullptr, n_seq, n_max, q_dev, workspace + w.fwd, train_mode, dropout_seed, dropout_step,
                                      stream)) != DTQN_OK)
         return rc;
+    if (greedy) return actor_greedy_rows(win + N, q_dev, q_last_host, action_host, N, n_max, net->num_actions, s);
     {
         ImgActorQArgs a;
         a.q = q_dev; a.win = win; a.q_last = q_last_host; a.n_envs = N; a.n_max = n_max; a.A = net->num_actions;
         IMG_LAUNCH(img_actor_qrows_kernel, (N * net->num_actions + IT - 1) / IT, 0, s, a);
     }
     return DTQN_OK;
+}
+
+extern "C" int dtqn_img_actor_forward_batch(const DtqnNet* net, const float* theta, float* wprep, int refresh_prep, const void* stage_host,
+                                            uint8_t* frame_ring, float* emb_ring, int n_envs, float* q_dev, float* q_last_host,
+                                            float* workspace, int train_mode, uint32_t dropout_seed, uint32_t dropout_step, void* stream) {
+    return img_actor_run(net, theta, wprep, refresh_prep, stage_host, frame_ring, emb_ring, n_envs, q_dev, q_last_host, nullptr, workspace,
+                         train_mode, dropout_seed, dropout_step, stream);
+}
+
+extern "C" int dtqn_img_actor_greedy_batch(const DtqnNet* net, const float* theta, float* wprep, int refresh_prep, const void* stage_host,
+                                           uint8_t* frame_ring, float* emb_ring, int n_envs, float* q_dev, float* q_last_host,
+                                           int32_t* action_host, float* workspace, int train_mode, uint32_t dropout_seed,
+                                           uint32_t dropout_step, void* stream) {
+    if (!q_last_host || !action_host) return DTQN_ERR_ARG;          // (no push-only form: an evaluation step always acts)
+    return img_actor_run(net, theta, wprep, refresh_prep, stage_host, frame_ring, emb_ring, n_envs, q_dev, q_last_host, action_host, workspace,
+                         train_mode, dropout_seed, dropout_step, stream);
 }

@@ -369,6 +369,23 @@ int dtqn_actor_forward(const DtqnNet* net, const float* theta, const void* ctx_h
 int dtqn_actor_forward_batch(const DtqnNet* net, const float* theta, const void* ctx_host, void* ctx_dev, int n_envs, int n_max,
                              float* q_dev, float* q_last_host, float* workspace, int train_mode, uint32_t dropout_seed,
                              uint32_t dropout_step, void* stream);
+/* Greedy evaluation on the batched actor (the reference plays its evaluation episodes one environment and one forward per step,
+ * run.py:187-243; here N evaluation environments share one launch until their episodes run out).  Arguments and block layout of
+ * dtqn_actor_forward_batch, plus a PINNED int32 action_host[N].  len_i == 0 marks environment i as IDLE (its episodes are played):
+ * the len block the caller staged is the single source of which environments are live -- the host takes the live count from it,
+ * the kernels read the same numbers in place, nothing is read back.  Stages on `stream`: a compaction kernel reads the pinned block
+ * and writes the live contexts, in environment order, to sequences 0 .. live - 1 of ctx_dev (fixed order, no atomics; no
+ * hipMemcpyAsync); the forward of dtqn_actor_forward_batch over `live` sequences of n_max rows (n_max >= every len_i: the maximum
+ * over the live environments); one kernel that writes, for a live environment, Q of row len_i - 1 to q_last_host[i][num_actions]
+ * and its arg-max -- first maximum on ties, as torch.argmax -- to action_host[i], and for an idle one action_host[i] = -1 while
+ * q_last_host[i] stays untouched (valid once `stream` has drained).  q_dev: [live][n_max][num_actions].  workspace as
+ * dtqn_actor_forward_batch for N.  All environments idle: action_host is filled with -1, nothing is launched, returns 0.
+ * Covers every network dtqn_actor_forward_batch covers (whole-sequence and row-block; bag networks: dtqn_forward_bag). */
+int dtqn_actor_greedy_batch(const DtqnNet* net, const float* theta, const void* ctx_host, void* ctx_dev, int n_envs, int n_max,
+                            float* q_dev, float* q_last_host, int32_t* action_host, float* workspace, int train_mode,
+                            uint32_t dropout_seed, uint32_t dropout_step, void* stream);
+/* Tests: live sequences (the forward's batch) of the last dtqn_actor_greedy_batch / dtqn_img_actor_greedy_batch. */
+int dtqn_debug_last_actor_live(void);
 /* DTQN.forward with the bag arguments (dtqn.py:158-218 incl. :201-214): bag_obs [B][bag_size][O] f32, bag_actions [B][bag_size] u8
  * (NULL when action_dim == 0).  Row-block tiled path; workspace as dtqn_forward_tiled.
  * train_mode != 0 with net->dropout > 0: a train-mode forward (the reference's policy network stays in train mode while the agent
@@ -563,7 +580,17 @@ long long dtqn_img_actor_workspace_floats(const DtqnNet* net, int n_envs);
 int dtqn_img_actor_forward_batch(const DtqnNet* net, const float* theta, float* wprep, int refresh_prep, const void* stage_host,
                                  uint8_t* frame_ring, float* emb_ring, int n_envs, float* q_dev, float* q_last_host, float* workspace,
                                  int train_mode, uint32_t dropout_seed, uint32_t dropout_step, void* stream);
-/* Tests: frames the last dtqn_img_actor_forward_batch encoded. */
+/* Greedy evaluation of image observations (run.py:187-243): dtqn_img_actor_forward_batch with idle environments and the arg-max on
+ * the device, as dtqn_actor_greedy_batch.  len_i == 0 marks environment i as idle: it pushes no frame (fresh_i is ignored),
+ * contributes no token to the encoder lists, none of its frame_ring / emb_ring rows is written and it occupies no sequence of the
+ * row-block forward (the live environments are compacted in order by the list kernel; q_dev: [live][n_max][num_actions]).  The token
+ * count is taken on the host from the same flags (dtqn_debug_last_img_actor_tokens).  action_host: PINNED int32 [N]; q_last_host
+ * and action_host as dtqn_actor_greedy_batch.  There is no push-only form.  With valid marks that the caller clears only when theta
+ * moves, an evaluation under frozen parameters encodes every frame exactly once. */
+int dtqn_img_actor_greedy_batch(const DtqnNet* net, const float* theta, float* wprep, int refresh_prep, const void* stage_host,
+                                uint8_t* frame_ring, float* emb_ring, int n_envs, float* q_dev, float* q_last_host, int32_t* action_host,
+                                float* workspace, int train_mode, uint32_t dropout_seed, uint32_t dropout_step, void* stream);
+/* Tests: frames the last dtqn_img_actor_forward_batch / dtqn_img_actor_greedy_batch encoded. */
 int dtqn_debug_last_img_actor_tokens(void);
 
 /* ------------------------------------------------------------------------------------------

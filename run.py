@@ -8,7 +8,7 @@ Differences from the reference, all at the edges of the hot path:
   * `--envs` defaults to the LIST ["DiscreteCarFlag-v0"] (the reference's string default iterates
     over characters, SURVEY.md section 4 quirk 7);
   * `--model` accepts DTQN only; `--render` is out of scope; pixel observations (`Box(0, 255, (C, H, W), uint8)`) run, with
-    `--num-envs N` too;
+    `--num-envs N` and `--eval-envs N` too;
   * new flags: `--sampler {reference,device}` (replay index draw on the host with Python's `random`
     stream like the reference, or on the GPU), `--ref-quirks` (reproduce the reference's
     int-truncated actor context), `--prepopulate N` (the reference hard-codes 50 000);
@@ -75,6 +75,9 @@ def get_args(argv: Optional[Sequence[str]] = None):
     p.add_argument("--overlap", action="store_true",
                    help="pipeline the actor forward of step t+1 with TD update t+1 on two HIP streams (same policy-vs-action "
                         "semantics; an episode that ends at step t becomes sampleable one update later)")
+    p.add_argument("--eval-envs", type=int, default=1,
+                   help="evaluation environments per domain: N > 1 plays the evaluation episodes N at a time through one batched greedy "
+                        "launch per step (dtqn_amd.agents.vector.VectorEvaluator); 1 evaluates through the single-environment actor")
     return p.parse_args(argv)
 
 
@@ -138,12 +141,13 @@ def prepopulate(agent, prepop_steps: int, envs) -> None:
 
 def train(agent, envs, eval_envs, env_strs, total_steps, eps, eval_frequency, eval_episodes, policy_path, save_policy,
           logger, mean_success_rate, mean_episode_length, mean_reward, time_remaining, verbose=False, is_main=True,
-          overlap=False, vector=None):
+          overlap=False, vector=None, evaluators=None):
     """Main loop: one env step, one TD update (run.py:246-353).  vector: a VectorActor over N environments; then one iteration in
     N steps all N environments at once with that vector step's N updates queued behind the actor forward (the other N - 1
     iterations only account for them), which keeps one update per env step.  The vector steps are driven by the updates still
     owed, not by `timestep % N`: a resumed run steps on its first iteration, and the time limit is only honoured at a
-    vector-step boundary, so a checkpoint's `num_train_steps` always equals the loop's timestep."""
+    vector-step boundary, so a checkpoint's `num_train_steps` always equals the loop's timestep.
+    evaluators: one VectorEvaluator per entry of env_strs (--eval-envs N > 1), used instead of evaluate() on eval_envs."""
     start = time()
     agent.eval_off()
     if vector is None:
@@ -180,8 +184,8 @@ def train(agent, envs, eval_envs, env_strs, total_steps, eps, eval_frequency, ev
                    "losses/Min_Q_Value": agent.qvalue_min.mean(), "losses/Max_Target_Value": agent.target_max.mean(),
                    "losses/Mean_Target_Value": agent.target_mean.mean(), "losses/Min_Target_Value": agent.target_min.mean(),
                    "losses/hours": hours}
-            for env_str, eval_env in zip(env_strs, eval_envs):
-                sr, ret, length = evaluate(agent, eval_env, eval_episodes)
+            for k, (env_str, eval_env) in enumerate(zip(env_strs, eval_envs)):
+                sr, ret, length = evaluate(agent, eval_env, eval_episodes) if evaluators is None else evaluators[k].evaluate(eval_episodes)
                 log.update({f"{env_str}/SuccessRate": sr, f"{env_str}/Return": ret, f"{env_str}/EpisodeLength": length})
                 if verbose and is_main:
                     print(f"[ {timestamp()} ] Training Steps: {timestep}, Env: {env_str}, Success Rate: {sr:.2f}, "
@@ -239,6 +243,8 @@ def run_experiment(args):
         f"gate={args.gate}_identity={args.identity}_history={args.history}_pos={args.pos}_bag={args.bag_size}_seed={args.seed}")
     if args.render:
         raise NotImplementedError("--render is outside dtqn_amd's scope")
+    if args.eval_envs < 1:
+        raise ValueError("--eval-envs must be at least 1")
     if os.path.exists(policy_path + "_mini_checkpoint.pt"):
         done_steps = agent.load_mini_checkpoint(policy_path)["step"]
         print(f"Found a mini checkpoint that completed {done_steps} training steps.")
@@ -263,9 +269,19 @@ def run_experiment(args):
         for k, e in enumerate(venvs):
             e.seed(args.seed + 1000 * (rank + 1) + k)
         vector = VectorActor(agent, venvs, ref_quirks=args.ref_quirks)
+    evaluators = None
+    if args.eval_envs > 1:
+        from dtqn_amd.agents.vector import VectorEvaluator
+        # N copies of every evaluation domain, seeded like the --num-envs copies (in a range of their own)
+        evaluators = []
+        for d, env_str in enumerate(args.envs):
+            copies = [env_processing.make_env(env_str) for _ in range(args.eval_envs)]
+            for k, e in enumerate(copies):
+                e.seed(args.seed + 1000 * (rank + 1) + 500 + d * args.eval_envs + k)
+            evaluators.append(VectorEvaluator(agent, copies, ref_quirks=args.ref_quirks))
     train(agent, envs, eval_envs, args.envs, args.num_steps, eps, args.eval_frequency, args.eval_episodes, policy_path,
           args.save_policy, logger, mean_success_rate, mean_reward, mean_episode_length, time_remaining, args.verbose, is_main,
-          overlap=args.overlap, vector=vector)
+          overlap=args.overlap, vector=vector, evaluators=evaluators)
     if is_main:
         agent.save_mini_checkpoint(checkpoint_dir=policy_path, wandb_id=None)
     return agent
