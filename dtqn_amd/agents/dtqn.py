@@ -37,6 +37,10 @@ NONFINITE_MESSAGE = ("The total norm of order 2.0 for gradients from `parameters
                      "and scale the gradients by the non-finite norm anyway, set `error_if_nonfinite=False`")
 
 
+def _live_rows(ctx) -> int:         # rows of a rolling context that hold a step of the episode: the unpadded prefix the actor forwards
+    return min(ctx.max_length, ctx.timestep + 1)
+
+
 class TrainMode(Enum):
     TRAIN = 1
     EVAL = 2
@@ -191,10 +195,19 @@ class DtqnAgent:
         self.train_mode = TrainMode.TRAIN
 
     # ---- actor (dtqn.py:76-160) -----------------------------------------------------------------
+    def _actor_drop_key(self, module_forward: bool = False):
+        """(seed, step) of the next actor forward's dropout masks; the step is the count of actor forwards that took a key.  The
+        C-kernel paths (dtqn_actor_forward, the batched entry points) take one for every forward; the paths through DTQN.forward
+        (module_forward; the reference's policy network is in train mode there, dqn.py:102-115) only in train mode with p > 0."""
+        if module_forward and not (self.train_mode == TrainMode.TRAIN and self.policy_network.dropout_p > 0.0):
+            return None
+        self._actor_calls += 1
+        return int(self.engine.td.dropout_seed) ^ 0xAC70, self._actor_calls
+
     def _launch_actor_forward(self, stream_ptr) -> int:
         """Stage the unpadded prefix of the rolling context and launch the batch-1 forward; returns n."""
         ctx = self.context
-        n = min(ctx.max_length, ctx.timestep + 1)
+        n = _live_rows(ctx)
         self._ctx_obs_np[:n] = ctx.obs[:n]
         self._ctx_act_np[:n] = ctx.action[:n, 0]
         eng = self.engine
@@ -205,10 +218,9 @@ class DtqnAgent:
         # pinned context -> device, forward, Q of the LAST timestep -> pinned: one library call, all on `stream_ptr`
         # the reference's policy network is in train mode during rollouts (dqn.py:102-115): with dropout > 0 the action
         # forward drops units too; evaluation (eval_on) runs without.  Keyed by the count of actor forwards.
-        self._actor_calls += 1
+        seed, step = self._actor_drop_key()
         rc = eng.lib.dtqn_actor_forward(eng._actor_net_ref, self._theta_p, self._ctx_hp, self._ctx_dp, n, self._q_p, self._q_hp,
-                                        self._actor_ws_p, 1 if self.train_mode == TrainMode.TRAIN else 0, eng.td.dropout_seed ^ 0xAC70,
-                                        self._actor_calls & 0xFFFFFFFF, stream_ptr)
+                                        self._actor_ws_p, 1 if self.train_mode == TrainMode.TRAIN else 0, seed, step & 0xFFFFFFFF, stream_ptr)
         if rc == B.DEFINES["DTQN_ERR_ARG"]:
             raise AssertionError("Cannot forward, history is longer than expected.")   # dtqn.py:170-173
         if rc != 0:
@@ -218,28 +230,18 @@ class DtqnAgent:
     def _bag_forward(self, obs: np.ndarray, actions: np.ndarray, bag_obss: np.ndarray, bag_actions: np.ndarray) -> torch.Tensor:
         """policy_network(obs, actions, bag_obss, bag_actions) on host arrays (batch-first); Q stays on the device."""
         t = lambda a, dt: torch.as_tensor(a, dtype=dt, device=self.device)
-        drop = None
-        if self.train_mode == TrainMode.TRAIN and self.policy_network.dropout_p > 0.0:
-            # the reference's policy network is in train mode here (dqn.py:102-115): fresh keep masks per forward, keyed like
-            # the plain actor's (seed ^ 0xAC70, count of actor forwards)
-            self._actor_calls += 1
-            drop = (int(self.engine.td.dropout_seed) ^ 0xAC70, self._actor_calls)
         return self.policy_network(t(obs, self.obs_tensor_type), t(actions, torch.long), t(bag_obss, self.obs_tensor_type),
-                                   t(bag_actions, torch.long), _train_dropout=drop)
+                                   t(bag_actions, torch.long), _train_dropout=self._actor_drop_key(module_forward=True))
 
     @torch.no_grad()
     def _image_action(self) -> int:
         """get_action of an image net (dtqn.py:79-108): the unpadded context prefix through DTQN.forward (convolutional embedding
         + row-block forward); the policy network is in train mode during rollouts like the reference's (dropout keyed per call)."""
         ctx = self.context
-        n = min(ctx.max_length, ctx.timestep + 1)
+        n = _live_rows(ctx)
         self._img_ctx_h[:n] = torch.from_numpy(ctx.obs[:n].reshape(n, -1))
-        drop = None
-        if self.train_mode == TrainMode.TRAIN and self.policy_network.dropout_p > 0.0:
-            self._actor_calls += 1
-            drop = (int(self.engine.td.dropout_seed) ^ 0xAC70, self._actor_calls)
         obs = self._img_ctx_h[:n].to(self.device, non_blocking=True).reshape(1, n, *self.image)
-        q = self.policy_network(obs, None, _train_dropout=drop)
+        q = self.policy_network(obs, None, _train_dropout=self._actor_drop_key(module_forward=True))
         return int(torch.argmax(q[0, -1]).item())
 
     @torch.no_grad()
@@ -247,20 +249,17 @@ class DtqnAgent:
         """get_action through DTQN.forward on the unpadded context prefix (dtqn.py:79-108): the route of a policy network with attention
         capture on, which then holds the acting context's weights (transformer_layers[i].alpha [1, n, n]), as the reference's does."""
         ctx = self.context
-        n = min(ctx.max_length, ctx.timestep + 1)
+        n = _live_rows(ctx)
         t = lambda a, dt: torch.as_tensor(a, dtype=dt, device=self.device)
-        drop = None
-        if self.train_mode == TrainMode.TRAIN and self.policy_network.dropout_p > 0.0:
-            self._actor_calls += 1
-            drop = (int(self.engine.td.dropout_seed) ^ 0xAC70, self._actor_calls)
-        q = self.policy_network(t(ctx.obs[None, :n], self.obs_tensor_type), t(ctx.action[None, :n], torch.long), _train_dropout=drop)
+        q = self.policy_network(t(ctx.obs[None, :n], self.obs_tensor_type), t(ctx.action[None, :n], torch.long),
+                                _train_dropout=self._actor_drop_key(module_forward=True))
         return int(torch.argmax(q[0, -1]).item())
 
     @torch.no_grad()
     def _bag_action(self) -> int:
         """get_action of a bag network (dtqn.py:79-108): the unpadded context prefix plus the WHOLE bag, padding included."""
         ctx = self.context
-        n = min(ctx.max_length, ctx.timestep + 1)
+        n = _live_rows(ctx)
         q = self._bag_forward(ctx.obs[None, :n], ctx.action[None, :n], self.bag.obss[None], self.bag.actions[None])
         return int(torch.argmax(q[:, -1, :]).item())
 

@@ -4,6 +4,7 @@
 // and behind it one small kernel writes Q of the last live row and its arg-max -- the greedy action (dtqn.py:103) -- for every
 // environment into pinned memory: the host reads N ints instead of taking N arg-maxes.
 #include "dtqn_actor.hpp"
+#include "dtqn_device.hpp"
 
 namespace dtqn {
 
@@ -92,15 +93,10 @@ __global__ __launch_bounds__(AT) void actor_greedy_kernel(ActorGreedyArgs a) {
 
 int actor_compact(const DtqnNet* net, const void* ctx_host, void* ctx_dev, int n_envs, int n_max, hipStream_t stream) {
     const int L = net->ctx_len, O = net->obs_dim;
-    const size_t obs_bytes = sizeof(float) * (size_t)n_envs * L * O;
-    const size_t act_bytes = (((size_t)n_envs * L) + 3) & ~(size_t)3;
+    const ActorBlock h = actor_block(net, ctx_host, n_envs), d = actor_block(net, ctx_dev, n_envs);
     ActorCompactArgs a;
-    a.obs_h = static_cast<const float*>(ctx_host);
-    a.act_h = static_cast<const uint8_t*>(ctx_host) + obs_bytes;
-    a.lens_h = reinterpret_cast<const int32_t*>(static_cast<const uint8_t*>(ctx_host) + obs_bytes + act_bytes);
-    a.obs_d = static_cast<float*>(ctx_dev);
-    a.act_d = static_cast<uint8_t*>(ctx_dev) + obs_bytes;
-    a.lens_d = reinterpret_cast<int32_t*>(static_cast<uint8_t*>(ctx_dev) + obs_bytes + act_bytes);
+    a.obs_h = h.obs; a.act_h = h.actions; a.lens_h = h.lens;
+    a.obs_d = d.obs; a.act_d = d.actions; a.lens_d = d.lens;
     a.n_envs = n_envs; a.L = L; a.O = O; a.n_max = n_max;
     const long long per = ((long long)n_max * O + 4 * AT - 1) / (4 * AT);        // four floats per thread, at most 64 workgroups per environment
     a.blocks_per_env = per < 1 ? 1 : per > 64 ? 64 : (int)per;

@@ -1,24 +1,25 @@
-// Pieces the batched actor entry points share (dtqn_actor.hip, dtqn_image.hip; dtqn_api.cpp declares the launchers itself: it is
-// host-only C++).
+// Host-side pieces the batched actor entry points share (dtqn_actor.hip, dtqn_image.hip, dtqn_api.cpp); no device code.
 #pragma once
-#include "dtqn_device.hpp"
+#include <hip/hip_runtime.h>
+
+#include "dtqn_hip.h"
 
 namespace dtqn {
 
-// Fixed-order compaction inside one workgroup of NT threads: thread t brings the count c of its own contiguous range and gets the
-// number of items the threads in front of it hold (inclusive scan in LDS, sums[NT]); no atomics.  Every thread of the workgroup calls it.
-template <int NT>
-__device__ __forceinline__ int block_scan_exclusive(int32_t* sums, int t, int c) {
-    __syncthreads();                     // (a caller may scan twice through the same array)
-    sums[t] = c;
-    __syncthreads();
-    for (int off = 1; off < NT; off <<= 1) {
-        const int v = t >= off ? sums[t - off] : 0;
-        __syncthreads();
-        sums[t] += v;
-        __syncthreads();
-    }
-    return sums[t] - c;
+// The packed block of the batched actor entry points, pinned host copy and device copy alike:
+// [N][ctx_len * obs_dim] f32 observations | [N][ctx_len] u8 actions, padded to 4 bytes | [N] i32 live rows.
+struct ActorBlock {
+    float* obs;
+    uint8_t* actions;
+    int32_t* lens;
+    size_t bytes;
+};
+inline ActorBlock actor_block(const DtqnNet* net, const void* base, int n_envs) {
+    const size_t obs_bytes = sizeof(float) * (size_t)n_envs * net->ctx_len * net->obs_dim;
+    const size_t act_bytes = (((size_t)n_envs * net->ctx_len) + 3) & ~(size_t)3;       // keeps the int32 block 4-byte aligned
+    uint8_t* p = static_cast<uint8_t*>(const_cast<void*>(base));
+    return ActorBlock{reinterpret_cast<float*>(p), p + obs_bytes, reinterpret_cast<int32_t*>(p + obs_bytes + act_bytes),
+                      obs_bytes + act_bytes + sizeof(int32_t) * (size_t)n_envs};
 }
 
 // Greedy evaluation (dtqn_actor_greedy_batch / dtqn_img_actor_greedy_batch): len_i == 0 marks environment i as idle.

@@ -3,6 +3,7 @@
 
 #include <cstdlib>
 
+#include "dtqn_actor.hpp"
 #include "dtqn_hip.h"
 #include "dtqn_limits.h"
 
@@ -135,9 +136,6 @@ int forward_infer(const DtqnNet* net, const float* theta, const float* obs, cons
                   uint32_t drop_seed, uint32_t drop_step, int train_mode);
 int tiled_forward_actor(const DtqnNet* net, const float* theta, const float* obs, const uint8_t* actions, int batch, int n, int in_rows,
                         float* q_out, float* workspace, int train_mode, uint32_t drop_seed, uint32_t drop_step, hipStream_t stream, const int32_t* lens = nullptr);
-int actor_compact(const DtqnNet* net, const void* ctx_host, void* ctx_dev, int n_envs, int n_max, hipStream_t stream);
-int actor_greedy_rows(const int32_t* lens, const float* q, float* q_last, int32_t* action, int n_envs, int n_max, int A, hipStream_t stream);
-void set_last_actor_live(int live);
 }
 extern "C" int dtqn_forward_tiled_strided(const DtqnNet* net, const float* theta, const float* obs, const uint8_t* actions,
                                           int batch, int n, int in_rows, float* q_out, float* workspace, void* stream);
@@ -176,18 +174,8 @@ extern "C" int dtqn_actor_forward(const DtqnNet* net, const float* theta, const 
     return DTQN_OK;
 }
 
-// The packed block of the batched actor entry points (pinned host copy and device copy alike), and the forward both run on it
-struct ActorBlock {
-    const float* obs;
-    const uint8_t* actions;
-    const int32_t* lens;
-};
-static ActorBlock actor_block(const DtqnNet* net, void* base, int n_envs) {
-    const size_t obs_bytes = sizeof(float) * (size_t)n_envs * net->ctx_len * net->obs_dim;
-    const size_t act_bytes = (((size_t)n_envs * net->ctx_len) + 3) & ~(size_t)3;       // keeps the int32 block 4-byte aligned
-    const uint8_t* p = static_cast<const uint8_t*>(base);
-    return ActorBlock{static_cast<const float*>(base), p + obs_bytes, reinterpret_cast<const int32_t*>(p + obs_bytes + act_bytes)};
-}
+// The forward both batched actor entry points run on the packed block (dtqn_actor.hpp)
+using dtqn::ActorBlock, dtqn::actor_block;
 // batch: sequences in the block (its first `batch` slots); ws_envs: the batch `workspace` was laid out for (>= batch).  Row-block nets
 // leave Q in q_dev only; the whole-sequence kernels also write row len_s - 1 of sequence s to q_last_host[s] when that is given.
 static int actor_batch_forward(const DtqnNet* net, const float* theta, const ActorBlock& b, int batch, int ws_envs, int n_max, float* q_dev,
@@ -217,23 +205,19 @@ extern "C" int dtqn_actor_forward_batch(const DtqnNet* net, const float* theta, 
     if (!net || !theta || !ctx_host || !ctx_dev || !q_dev || !q_last_host || n_envs < 1) return DTQN_ERR_ARG;
     if (n_max < 1 || n_max > net->ctx_len) return DTQN_ERR_ARG;                 // dtqn.py:170-173
     hipStream_t s = (hipStream_t)stream;
-    const int L = net->ctx_len;
-    const size_t obs_bytes = sizeof(float) * (size_t)n_envs * L * net->obs_dim;
-    const size_t act_bytes = (((size_t)n_envs * L) + 3) & ~(size_t)3;       // keeps the int32 block 4-byte aligned
-    const size_t total = obs_bytes + act_bytes + sizeof(int32_t) * (size_t)n_envs;
     // the live-row counts index q_dev (tiled path) and name the rows the kernel reports (whole-sequence path): the pinned host
     // copy is already written, so a bad count is refused here instead of becoming an out-of-bounds device access
-    const int32_t* lens_h = reinterpret_cast<const int32_t*>(static_cast<const uint8_t*>(ctx_host) + obs_bytes + act_bytes);
+    const ActorBlock h = actor_block(net, ctx_host, n_envs);
     for (int i = 0; i < n_envs; ++i)
-        if (lens_h[i] < 1 || lens_h[i] > n_max) return DTQN_ERR_ARG;
-    if (hipMemcpyAsync(ctx_dev, ctx_host, total, hipMemcpyHostToDevice, s) != hipSuccess) return DTQN_ERR_LAUNCH;
+        if (h.lens[i] < 1 || h.lens[i] > n_max) return DTQN_ERR_ARG;
+    if (hipMemcpyAsync(ctx_dev, ctx_host, h.bytes, hipMemcpyHostToDevice, s) != hipSuccess) return DTQN_ERR_LAUNCH;
     const ActorBlock b = actor_block(net, ctx_dev, n_envs);
     const int rc = actor_batch_forward(net, theta, b, n_envs, n_envs, n_max, q_dev, q_last_host, workspace, train_mode, dropout_seed,
                                        dropout_step, stream);
     if (rc != DTQN_OK || !net->tiled) return rc;
     // row-block tiled nets: the forward leaves Q in q_dev; the last rows come back with one small copy per actor
     for (int i = 0; i < n_envs; ++i)
-        if (hipMemcpyAsync(q_last_host + (size_t)i * net->num_actions, q_dev + ((size_t)i * n_max + (lens_h[i] - 1)) * net->num_actions,
+        if (hipMemcpyAsync(q_last_host + (size_t)i * net->num_actions, q_dev + ((size_t)i * n_max + (h.lens[i] - 1)) * net->num_actions,
                            sizeof(float) * net->num_actions, hipMemcpyDeviceToHost, s) != hipSuccess)
             return DTQN_ERR_LAUNCH;
     return DTQN_OK;
@@ -249,7 +233,7 @@ extern "C" int dtqn_actor_greedy_batch(const DtqnNet* net, const float* theta, c
                                        int train_mode, uint32_t dropout_seed, uint32_t dropout_step, void* stream) {
     if (!net || !theta || !ctx_host || !ctx_dev || !q_dev || !q_last_host || !action_host || n_envs < 1) return DTQN_ERR_ARG;
     if (n_max < 0 || n_max > net->ctx_len) return DTQN_ERR_ARG;                 // dtqn.py:170-173
-    const ActorBlock h = actor_block(net, const_cast<void*>(ctx_host), n_envs);
+    const ActorBlock h = actor_block(net, ctx_host, n_envs);
     int live = 0;
     for (int i = 0; i < n_envs; ++i) {
         if (h.lens[i] < 0 || h.lens[i] > n_max) return DTQN_ERR_ARG;

@@ -1119,4 +1119,21 @@ __device__ __forceinline__ const float* layer_theta(const DtqnNet& net, const fl
     return theta + net.off_layer0 + (size_t)l * net.layer_stride;
 }
 
+
+// Fixed-order compaction inside one workgroup of NT threads: thread t brings the count c of its own contiguous range and gets the
+// number of items the threads in front of it hold (inclusive scan in LDS, sums[NT]); no atomics.  Every thread of the workgroup calls it.
+template <int NT>
+__device__ __forceinline__ int block_scan_exclusive(int32_t* sums, int t, int c) {
+    __syncthreads();                     // (a caller may scan twice through the same array)
+    sums[t] = c;
+    __syncthreads();
+    for (int off = 1; off < NT; off <<= 1) {
+        const int v = t >= off ? sums[t - off] : 0;
+        __syncthreads();
+        sums[t] += v;
+        __syncthreads();
+    }
+    return sums[t] - c;
+}
+
 }  // namespace dtqn

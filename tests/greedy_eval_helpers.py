@@ -26,15 +26,10 @@ def live_lens(L):
 
 def stage(net, lens, obs_list, act_list, device):
     """The packed block of dtqn_actor_forward_batch for len(lens) environments (len 0: nothing staged) -> (ctx_h, n_max)."""
+    from dtqn_amd.agents.vector import actor_block
     L, Od, N = net.ctx_len, net.obs_dim, len(lens)
-    obs_bytes, act_bytes = N * L * Od * 4, (N * L + 3) & ~3
-    ctx_h = torch.zeros(obs_bytes + act_bytes + 4 * N, dtype=torch.uint8)
-    if device != "cpu":
-        ctx_h = ctx_h.pin_memory()
-    buf = ctx_h.numpy()
-    o = buf[:obs_bytes].view(np.float32).reshape(N, L, Od)
-    a = buf[obs_bytes:obs_bytes + N * L].reshape(N, L)
-    ln = buf[obs_bytes + act_bytes:].view(np.int32)
+    pin = (lambda t: t.pin_memory()) if device != "cpu" else (lambda t: t)
+    _, ctx_h, o, a, ln = actor_block(N, L, Od, lambda nbytes: pin(torch.zeros(nbytes, dtype=torch.uint8)))
     for i, n in enumerate(lens):
         ln[i] = n
         if n > 0:

@@ -78,23 +78,23 @@ def run(a, n_envs, mode, device):
         vec.reset_all()
         one = lambda: vec.step_all(0.0, updates=0 if frozen else 1)
 
-        def clocked(name):
-            inner = getattr(vec, name)
-            host[name] = 0.0
+        def clocked(obj, name, key):
+            inner = getattr(obj, name)
+            host[key] = 0.0
 
             def f(*args, **kw):
                 t = time.perf_counter()
                 try:
                     return inner(*args, **kw)
                 finally:
-                    host[name] += time.perf_counter() - t
-            setattr(vec, name, f)
+                    host[key] += time.perf_counter() - t
+            setattr(obj, name, f)
     for _ in range(a.warmup):
         one()
     torch.cuda.synchronize()
     if n_envs > 1:
-        for name in ("_launch_q", "_wait_q", "_commit_episode"):
-            clocked(name)
+        for obj, name, key in ((vec._be, "launch", "launch_q"), (vec._be, "wait", "wait_q"), (vec, "_commit_episode", "commit_episode")):
+            clocked(obj, name, key)
     t0 = time.perf_counter()
     for _ in range(a.steps):
         one()

@@ -16,18 +16,12 @@ from helpers import net_from_cfg, pack_theta, ptr
 
 def run_batch(lib, net, theta, obs_list, act_list, device, stream=None, lens_override=None, n_max_override=None):
     """Pack N ragged prefixes the way VectorActor does and call the C entry point.  Returns (rc, q_last [N][A], q_all [N][n_max][A])."""
+    from dtqn_amd.agents.vector import actor_block
     L, Od, A, N = net.ctx_len, net.obs_dim, net.num_actions, len(obs_list)
-    obs_bytes, act_bytes = N * L * Od * 4, (N * L + 3) & ~3
-    total = obs_bytes + act_bytes + 4 * N
     cuda = device != "cpu"
-    ctx_h = torch.zeros(total, dtype=torch.uint8)
-    q_last = torch.full((N, A), float("nan"))
-    if cuda:
-        ctx_h, q_last = ctx_h.pin_memory(), q_last.pin_memory()
-    buf = ctx_h.numpy()
-    o = buf[:obs_bytes].view(np.float32).reshape(N, L, Od)
-    a = buf[obs_bytes:obs_bytes + N * L].reshape(N, L)
-    ln = buf[obs_bytes + act_bytes:].view(np.int32)
+    pin = (lambda t: t.pin_memory()) if cuda else (lambda t: t)
+    q_last = pin(torch.full((N, A), float("nan")))
+    total, ctx_h, o, a, ln = actor_block(N, L, Od, lambda nbytes: pin(torch.zeros(nbytes, dtype=torch.uint8)))
     n_max = 1
     for i, (ob, ac) in enumerate(zip(obs_list, act_list)):
         n = len(ob)
