@@ -39,15 +39,12 @@ __device__ __forceinline__ void tl_start_skew(int ticks) {
     }
 }
 // skew of a launch of nblk workgroups on `slots` resident ones: only where the last round is between a quarter and three quarters full
-// `ticks`: the kernel's own default -- the delay has to be a fair share of one workgroup's run time (measured at BASELINE config 4, forward
-// stage: the 60-us projection kernel 600; the fused layer kernel, 160 us: 0 -> 626 us, 600 -> 574, 1200 -> 558, 2400 -> 551, 4000 -> 575)
-static inline int tl_skew_ticks(int nblk, int slots, int ticks = 600, const char* own_env = nullptr) {
-    const char* e = own_env != nullptr ? getenv(own_env) : nullptr;
-    if (e == nullptr) e = getenv("DTQN_SKEW_TICKS");
+// (the per-launch half of the rule: packed and unpacked launches differ in nblk; `ticks`: the kernel's delay, TlFwdPlan)
+static inline int tl_skew_ticks(int nblk, int slots, int ticks) {
     const int rest = nblk % slots;
     // (only between one and two rounds: at two and a half -- config 3's packed launches, 1312 workgroups -- the same delay costs 11 us per forward)
     if (nblk <= slots || nblk >= 2 * slots || slots != 512 || rest * 4 < slots || rest * 4 > 3 * slots) return 0;
-    return e != nullptr ? atoi(e) : ticks;
+    return ticks;
 }
 
 constexpr int TNW = 8;                 // waves per workgroup of the GEMM / row-wise kernels
@@ -3391,14 +3388,14 @@ __global__ __launch_bounds__(TNT) void tl_copy_kernel(TlCopyArgs a) {
 }
 
 // ---- launch helpers --------------------------------------------------------------------------------------------------------
-// DTQN_TL_TRACE=1 (tests): one line per launch on stderr, so a test can tell WHICH kernels an update went through
-static inline bool tl_trace_on() {
-    const char* e = getenv("DTQN_TL_TRACE");                            // (read per launch: a test switches it on for one case)
-    return e != nullptr && e[0] == '1';
-}
+// DTQN_TL_TRACE=1 (tests): one line per launch on stderr, so a test can tell WHICH kernels an update went through and on what grid
+// (read per launch: a test switches it on for one case)
 #define TL_LAUNCH(kernel, grid, block, lds, stream, args)                                                            \
     do {                                                                                                             \
-        if (tl_trace_on()) fprintf(stderr, "tl_launch %s\n", #kernel);                                               \
+        if (tl_sw_one<TLSW_TL_TRACE>()) {                                                                            \
+            const dim3 tl_g_ = (grid), tl_b_ = (block);                                                              \
+            fprintf(stderr, "tl_launch %s grid=%u,%u,%u block=%u lds=%zu\n", #kernel, tl_g_.x, tl_g_.y, tl_g_.z, tl_b_.x, (size_t)(lds)); \
+        }                                                                                                            \
         if ((lds) > 48 * 1024) {            /* beyond the default dynamic-LDS limit: raise it once per kernel and device */   \
             static size_t tl_attr_lds_[kMaxDevices] = {};                                                            \
             raise_lds_limit(reinterpret_cast<const void*>(&kernel), (lds), tl_attr_lds_);                               \
@@ -3408,43 +3405,42 @@ static inline bool tl_trace_on() {
         if (hipGetLastError() != hipSuccess) return DTQN_ERR_LAUNCH;                                                 \
     } while (0)
 
+// ---- launch plans: every decision of a pass, made once --------------------------------------------------------------------------
+// forward_records / backward_records fill one of these at their top from the switches (dtqn_tl_switch.hpp) and the shape of the pass; the
+// layer loops and the launchers below read it and decide nothing themselves, so the row packing, the TAIL == 2 instantiation and the
+// launch that runs them cannot disagree about the rows per workgroup.
+
+// resident workgroups of the row kernels: two per compute unit at d_model <= 128, one at 256, on 256 compute units
+template <int D>
+constexpr int tl_slots() { return 256 * (D <= 128 ? 2 : 1); }
+
+// DTQN_GEMM_ROWS: rows per workgroup of the linear / dY W kernels
+enum TlGemmRows { TL_GEMM_64, TL_GEMM_32, TL_GEMM_AUTO };
+// ... per launch, because the launches of a pass differ in their column blocks (blocks64: the launch's 64-row workgroups)
+static bool tl_half_rows(TlGemmRows rows, int blocks64, int slots) {
+    if (rows != TL_GEMM_AUTO) return rows == TL_GEMM_32;
+    // 32 rows only for launches that would leave more than 40 % of their slots idle
+    const int rounds = (blocks64 + slots - 1) / slots;
+    return (rounds * slots - blocks64) * 100 > 40 * rounds * slots;
+}
 // Rows per workgroup of the linear / dY W kernels: 64.  The 32-row instantiations (DTQN_GEMM_ROWS=32) even out short launches
 // (768 workgroups on 512 slots; 256 for the backward products into a D-wide output) but fetch every weight fragment for half
 // the MFMAs: measured cfg 4 787 -> 748, cfg 5 445 -> 408 updates/s, so they stay an experiment switch.  (The fused feed-forward
-// kernel, whose workgroups run 8-16 weight fragments deep, gains from 32 rows: launch_ffn.)
-static bool tl_half_rows(int blocks64, int slots) {
-    const char* e = getenv("DTQN_GEMM_ROWS");
-    if (e == nullptr) return false;
-    if (e[0] == 'a') {                 // "auto" (experiment, round 4: cfg 5 485.5 -> 476.3, cfg 4 847.5 -> 840.0, cfg 3 508.2 -> 507.4: stays off):
-                                       // 32 rows only for launches that would leave more than 40 % of their slots idle
-        const int rounds = (blocks64 + slots - 1) / slots;
-        return (rounds * slots - blocks64) * 100 > 40 * rounds * slots;
-    }
-    return atoi(e) == 32;
+// kernel, whose workgroups run 8-16 weight fragments deep, gains from 32 rows: tl_rows32.)
+static TlGemmRows tl_gemm_rows() {
+    const TlSwInt e = tl_sw_int<TLSW_GEMM_ROWS>();
+    if (!e.set) return TL_GEMM_64;
+    // "auto" (experiment, round 4: cfg 5 485.5 -> 476.3, cfg 4 847.5 -> 840.0, cfg 3 508.2 -> 507.4: stays off)
+    if (e.c0 == 'a') return TL_GEMM_AUTO;
+    return e.v == 32 ? TL_GEMM_32 : TL_GEMM_64;
 }
-template <int D>
-static int launch_linear(TlLinearArgs a, int S, hipStream_t stream) {
-    const int cb = (a.N + 16 * TNW - 1) / (16 * TNW);
-    if (tl_half_rows(S * a.rpb * cb, 256 * (D <= 128 ? 2 : 1))) {
-        a.rpb *= 2;
-        const size_t lds = (size_t)32 * ((D > 16 * TNW ? D : 16 * TNW) + 4) * sizeof(float);   // operand tile, reused by the epilogue tile
-        if (D % 128 == 0 && a.Wpa != nullptr && a.Wpb != nullptr) TL_LAUNCH((tl_linear_kernel<D, 32, D % 128 == 0>), dim3(S * a.rpb, cb), dim3(TNT), lds, stream, a);
-        else TL_LAUNCH((tl_linear_kernel<D, 32, false>), dim3(S * a.rpb, cb), dim3(TNT), lds, stream, a);
-    } else {
-        const size_t lds = (size_t)64 * ((D > 16 * TNW ? D : 16 * TNW) + 4) * sizeof(float);
-        if (D % 128 == 0 && a.Wpa != nullptr && a.Wpb != nullptr) TL_LAUNCH((tl_linear_kernel<D, 64, D % 128 == 0>), dim3(S * a.rpb, cb), dim3(TNT), lds, stream, a);
-        else TL_LAUNCH((tl_linear_kernel<D, 64, false>), dim3(S * a.rpb, cb), dim3(TNT), lds, stream, a);
-    }
-    return DTQN_OK;
-}
-template <int D>
-static int launch_ffn_bwd(TlFfnBwdArgs a, int S, hipStream_t stream);
-// a.rpb on entry: 64-row blocks per sequence; rows per workgroup chosen like launch_ffn's (DTQN_FFN_ROWS forces)
-// `which`: the kernel's own switch (DTQN_ROWS_FFN / _FFNB / _WIDE = 32 | 64), else DTQN_FFN_ROWS for all three, else the rule
-static bool tl_rows32(int blocks64, int slots, int D, const char* which) {
-    const char* e = getenv(which);
-    if (e == nullptr) e = getenv("DTQN_FFN_ROWS");
-    if (e != nullptr) return atoi(e) == 32;
+// Rows per workgroup of the feed-forward, wide, layer and feed-forward-backward kernels for a pass of blocks64 64-row blocks.
+// `own`: the kernel family's switch (DTQN_ROWS_FFN / _FFNB / _WIDE = 32 | 64), else DTQN_FFN_ROWS for all three, else the rule:
+// 64-row workgroups by default; when the last round of 64-row workgroups would leave more than 15 % of the launch's slots idle
+// (resident workgroups: two per CU at D <= 128, one at D = 256), 32-row workgroups even the rounds out (cfg 4: 768 workgroups on
+// 512 slots = 1.5 rounds -> 1536 = 3, 764 -> 788 updates/s; cfg 5: 384 on 256 -> 768 = 3, 437 -> 445).
+static bool tl_rows32(TlSwInt own, int blocks64, int slots, int D) {
+    if (own.set) return own.v == 32;
     const int rounds = (blocks64 + slots - 1) / slots;
     // D = 256 (one workgroup per CU): 32 rows when the last round of 64-row workgroups would leave more than 15 % of the slots idle.
     // D <= 128 (two per CU), round 6: tools/microbench/mfma_probe.hip shows these loops bound by the weight fragments every workgroup
@@ -3455,83 +3451,126 @@ static bool tl_rows32(int blocks64, int slots, int D, const char* which) {
     if (D <= 128) return blocks64 * 2 < slots;
     return (rounds * slots - blocks64) * 100 > 15 * rounds * slots;
 }
+
+struct TlFwdPlan {
+    int slots;                         // tl_slots<D>()
+    int n_save;                        // sequences the backward reads again: the training third of a TD update
+    bool rows32_ffn, rows32_wide;      // 32-row workgroups: tl_ffn / tl_layer; tl_wide
+    TlGemmRows gemm_rows;              // tl_linear: per launch (tl_half_rows)
+    bool no_wide;                      // DTQN_NO_WIDE
+    bool fuse_tail;                    // everything behind the attention in one launch (tl_layer_kernel)
+    bool embed_table_qkv;              // a table embedding launch also runs layer 0's q | k | v projection
+    bool qkv_fuse;                     // the layer launch can carry the next layer's q | k | v projection (TAIL == 2)
+    TlPack pack;                       // packed rows of the passes nobody reads again (L == 0: none) ...
+    int nblk_rows;                     // ... and the workgroups of such a launch
+    bool attn_kblock, bag_mfma;        // key-blocked attention; matrix-core bag attention
+    int skew_ffn, skew_wide, skew_layer;   // start-skew ticks of a launch that tl_skew_ticks finds a round and a half long
+};
+struct TlBwdPlan {
+    bool head_fuse;                    // the Q-head backward rides in the dL/dxf product
+    bool chain;                        // tl_chain_bwd_kernel
+    bool ffn_bwd;                      // the fused feed-forward backward (where the chain does not run)
+    bool rows32_ffnb;                  // 32-row workgroups: tl_ffn_bwd
+    TlGemmRows gemm_rows;              // tl_dx: per launch (tl_half_rows)
+    bool attn_kblock, bag_mfma;
+};
+
+// The key-blocked kernels (tl_attn_kb_*) take over exactly where the whole-head tile does not fit LDS (dtqn_attn_whole_tile, the test
+// dtqn_net_init admits shapes by); DTQN_ATTN_KBLOCK=1 (A/B and tests) forces them on any row-block shape.
+static inline bool tl_attn_kblock(const DtqnNet& net) {
+    return tl_sw_one<TLSW_ATTN_KBLOCK>() || !dtqn_attn_whole_tile(net.lp, net.head_dim);
+}
+// Bag attention: the matrix-core kernels (tl_bag_attn_mfma_*) take over exactly where the resident backward's LDS request at the network's
+// full context does not fit a workgroup (dtqn_bag_attn_resident) -- by ctx_len and not by the live row count of one call, so that every
+// forward and backward of a network runs the same family; DTQN_BAG_ATTN_MFMA=1 (A/B and tests) forces them on any bag.
+static inline bool tl_bag_mfma(const DtqnNet& net) {
+    return tl_sw_one<TLSW_BAG_ATTN_MFMA>() || !dtqn_bag_attn_resident(net.ctx_len, net.bag_size, net.head_dim);
+}
+
+template <int D, int MR>
+static int launch_linear_rows(const TlLinearArgs& a, int S, int cb, hipStream_t stream) {
+    const size_t lds = (size_t)MR * ((D > 16 * TNW ? D : 16 * TNW) + 4) * sizeof(float);   // operand tile, reused by the epilogue tile
+    if (D % 128 == 0 && a.Wpa != nullptr && a.Wpb != nullptr) TL_LAUNCH((tl_linear_kernel<D, MR, D % 128 == 0>), dim3(S * a.rpb, cb), dim3(TNT), lds, stream, a);
+    else TL_LAUNCH((tl_linear_kernel<D, MR, false>), dim3(S * a.rpb, cb), dim3(TNT), lds, stream, a);
+    return DTQN_OK;
+}
+// a.rpb on entry (here and below): 64-row blocks per sequence
 template <int D>
-static int launch_ffn_bwd(TlFfnBwdArgs a, int S, hipStream_t stream) {
-    if (tl_rows32(S * a.rpb, 256 * (D <= 128 ? 2 : 1), D, "DTQN_ROWS_FFNB")) {
-        a.rpb *= 2;
-        const size_t lds = (size_t)32 * ((D + 4) + (128 + 4)) * sizeof(float);
-        if (D % 128 == 0 && a.W1p != nullptr && a.W2p != nullptr) TL_LAUNCH((tl_ffn_bwd_kernel<D, 32, D % 128 == 0>), dim3(S * a.rpb), dim3(TNT), lds, stream, a);
-        else TL_LAUNCH((tl_ffn_bwd_kernel<D, 32, false>), dim3(S * a.rpb), dim3(TNT), lds, stream, a);
-    } else {
-        const size_t lds = (size_t)64 * ((D + 4) + (128 + 4)) * sizeof(float);
-        if (D % 128 == 0 && a.W1p != nullptr && a.W2p != nullptr) TL_LAUNCH((tl_ffn_bwd_kernel<D, 64, D % 128 == 0>), dim3(S * a.rpb), dim3(TNT), lds, stream, a);
-        else TL_LAUNCH((tl_ffn_bwd_kernel<D, 64, false>), dim3(S * a.rpb), dim3(TNT), lds, stream, a);
-    }
+static int launch_linear(TlLinearArgs a, int S, const TlFwdPlan& plan, hipStream_t stream) {
+    const int cb = (a.N + 16 * TNW - 1) / (16 * TNW);
+    if (!tl_half_rows(plan.gemm_rows, S * a.rpb * cb, plan.slots)) return launch_linear_rows<D, 64>(a, S, cb, stream);
+    a.rpb *= 2;
+    return launch_linear_rows<D, 32>(a, S, cb, stream);
+}
+template <int D, int MR>
+static int launch_ffn_bwd_rows(const TlFfnBwdArgs& a, int S, hipStream_t stream) {
+    const size_t lds = (size_t)MR * ((D + 4) + (128 + 4)) * sizeof(float);
+    if (D % 128 == 0 && a.W1p != nullptr && a.W2p != nullptr) TL_LAUNCH((tl_ffn_bwd_kernel<D, MR, D % 128 == 0>), dim3(S * a.rpb), dim3(TNT), lds, stream, a);
+    else TL_LAUNCH((tl_ffn_bwd_kernel<D, MR, false>), dim3(S * a.rpb), dim3(TNT), lds, stream, a);
     return DTQN_OK;
 }
 template <int D>
+static int launch_ffn_bwd(TlFfnBwdArgs a, int S, const TlBwdPlan& plan, hipStream_t stream) {
+    if (!plan.rows32_ffnb) return launch_ffn_bwd_rows<D, 64>(a, S, stream);
+    a.rpb *= 2;
+    return launch_ffn_bwd_rows<D, 32>(a, S, stream);
+}
+// (64-row workgroups only: the LayerNorm column partials are per 64-row block)
+template <int D>
 static int launch_chain_bwd(const TlChainBwdArgs& a, int S, hipStream_t stream) {
-    {
-        const size_t lds = ((size_t)64 * ((D + 4) + (128 + 4)) + (size_t)TNW * 2 * D) * sizeof(float);
-        if (D % 128 == 0 && a.f.W1p != nullptr && a.f.W2p != nullptr && a.Wop != nullptr) TL_LAUNCH((tl_chain_bwd_kernel<D, D % 128 == 0>), dim3(S * a.f.rpb), dim3(TNT), lds, stream, a);
-        else TL_LAUNCH((tl_chain_bwd_kernel<D, false>), dim3(S * a.f.rpb), dim3(TNT), lds, stream, a);
-        return DTQN_OK;
-    }
+    const size_t lds = ((size_t)64 * ((D + 4) + (128 + 4)) + (size_t)TNW * 2 * D) * sizeof(float);
+    if (D % 128 == 0 && a.f.W1p != nullptr && a.f.W2p != nullptr && a.Wop != nullptr) TL_LAUNCH((tl_chain_bwd_kernel<D, D % 128 == 0>), dim3(S * a.f.rpb), dim3(TNT), lds, stream, a);
+    else TL_LAUNCH((tl_chain_bwd_kernel<D, false>), dim3(S * a.f.rpb), dim3(TNT), lds, stream, a);
+    return DTQN_OK;
 }
 template <int D, int MR>
-static int launch_wide_rows(TlWideArgs a, int nblk, bool ln, bool pk, size_t lds, hipStream_t stream) {
+static int launch_wide_rows(TlWideArgs a, int nblk, const TlFwdPlan& plan, hipStream_t stream) {
     constexpr bool CAN = D % 128 == 0;                                 // fragment-major weights exist for these widths
-    a.skew = tl_skew_ticks(nblk, 256 * (D <= 128 ? 2 : 1), 600, "DTQN_SKEW_WIDE");
+    const bool ln = a.ln_out.base != nullptr, pk = CAN && a.Wpa != nullptr && a.Wpb != nullptr;
+    const size_t lds = MR * (ln ? (size_t)2 * (D + 4) : (size_t)(D + 4) + (128 + 4)) * sizeof(float);
+    a.skew = tl_skew_ticks(nblk, plan.slots, plan.skew_wide);
     if (ln && pk) TL_LAUNCH((tl_wide_kernel<D, MR, true, CAN>), dim3(nblk), dim3(TNT), lds, stream, a);
     else if (ln) TL_LAUNCH((tl_wide_kernel<D, MR, true, false>), dim3(nblk), dim3(TNT), lds, stream, a);
     else if (pk) TL_LAUNCH((tl_wide_kernel<D, MR, false, CAN>), dim3(nblk), dim3(TNT), lds, stream, a);
     else TL_LAUNCH((tl_wide_kernel<D, MR, false, false>), dim3(nblk), dim3(TNT), lds, stream, a);
     return DTQN_OK;
 }
-// nblk_rows > 0: a packed launch (TlPack) of that many 64-row workgroups
+// a.pack.L > 0: a packed launch (TlPack) of plan.nblk_rows 64-row workgroups; the plan packs only where this launch runs 64 rows
 template <int D>
-static int launch_wide(TlWideArgs a, int S, hipStream_t stream, int nblk_rows = 0) {
-    const bool ln = a.ln_out.base != nullptr;
-    const size_t cols = ln ? (size_t)2 * (D + 4) : (size_t)(D + 4) + (128 + 4);
-    const bool pk = D % 128 == 0 && a.Wpa != nullptr && a.Wpb != nullptr;
-    if (tl_rows32(S * a.rpb, 256 * (D <= 128 ? 2 : 1), D, "DTQN_ROWS_WIDE")) {
-        a.rpb *= 2;
-        a.pack = TlPack{0, 0, 0};
-        return launch_wide_rows<D, 32>(a, S * a.rpb, ln, pk, 32 * cols * sizeof(float), stream);
-    }
-    if (a.pack.L > 0 && !ln && nblk_rows > 0) return launch_wide_rows<D, 64>(a, nblk_rows, ln, pk, 64 * cols * sizeof(float), stream);
-    a.pack = TlPack{0, 0, 0};
-    return launch_wide_rows<D, 64>(a, S * a.rpb, ln, pk, 64 * cols * sizeof(float), stream);
+static int launch_wide(TlWideArgs a, int S, const TlFwdPlan& plan, hipStream_t stream) {
+    if (a.pack.L > 0 && (plan.rows32_wide || a.ln_out.base != nullptr)) return DTQN_ERR_CONFIG;
+    if (a.pack.L > 0) return launch_wide_rows<D, 64>(a, plan.nblk_rows, plan, stream);
+    if (!plan.rows32_wide) return launch_wide_rows<D, 64>(a, S * a.rpb, plan, stream);
+    a.rpb *= 2;
+    return launch_wide_rows<D, 32>(a, S * a.rpb, plan, stream);
 }
-// a.rpb on entry: 64-row blocks per sequence.  64-row workgroups by default; when the last round of 64-row workgroups would
-// leave more than 15 % of the launch's slots idle (resident workgroups: two per CU at D <= 128, one at D = 256), 32-row
-// workgroups even the rounds out (cfg 4: 768 workgroups on 512 slots = 1.5 rounds -> 1536 = 3, 764 -> 788 updates/s; cfg 5: 384
-// on 256 -> 768 = 3, 437 -> 445).  DTQN_FFN_ROWS=32|64 forces one.
 template <int D, int MR>
-static int launch_ffn_rows(TlFfnArgs a, int nblk, bool pk, hipStream_t stream) {
+static int launch_ffn_rows(TlFfnArgs a, int nblk, const TlFwdPlan& plan, hipStream_t stream) {
     const size_t lds = (size_t)MR * ((D + 4) + (128 + 4)) * sizeof(float);
-    a.skew = tl_skew_ticks(nblk, 256 * (D <= 128 ? 2 : 1));
+    const bool pk = D % 128 == 0 && a.W1pa != nullptr && a.W1pb != nullptr && a.W2pa != nullptr && a.W2pb != nullptr;
+    a.skew = tl_skew_ticks(nblk, plan.slots, plan.skew_ffn);
     if (pk) TL_LAUNCH((tl_ffn_kernel<D, MR, D % 128 == 0>), dim3(nblk), dim3(TNT), lds, stream, a);
     else TL_LAUNCH((tl_ffn_kernel<D, MR, false>), dim3(nblk), dim3(TNT), lds, stream, a);
     return DTQN_OK;
 }
 template <int D>
-static int launch_ffn(TlFfnArgs a, int S, hipStream_t stream) {
-    const int blocks64 = S * a.rpb, slots = 256 * (D <= 128 ? 2 : 1);
-    const bool pk = D % 128 == 0 && a.W1pa != nullptr && a.W1pb != nullptr && a.W2pa != nullptr && a.W2pb != nullptr;
-    if (tl_rows32(blocks64, slots, D, "DTQN_ROWS_FFN")) {
-        a.rpb *= 2;
-        return launch_ffn_rows<D, 32>(a, S * a.rpb, pk, stream);
-    }
-    return launch_ffn_rows<D, 64>(a, S * a.rpb, pk, stream);
+static int launch_ffn(TlFfnArgs a, int S, const TlFwdPlan& plan, hipStream_t stream) {
+    if (!plan.rows32_ffn) return launch_ffn_rows<D, 64>(a, S * a.rpb, plan, stream);
+    a.rpb *= 2;
+    return launch_ffn_rows<D, 32>(a, S * a.rpb, plan, stream);
 }
 static int g_last_packed_blocks = 0;    // grid of the last fused-layer launch if it was a packed one, else 0 (tests: dtqn_debug_last_packed_blocks)
 // the fused layer tail: rows per workgroup by launch_ffn's rule (its long phase is the feed-forward loop)
+// tail: 0 none, 1 the Q head, 2 the next layer's q | k | v projection
 template <int D, int MR>
-static int launch_layer_rows(TlLayerArgs a, int nblk, bool pk, int tail, hipStream_t stream) {
+static int launch_layer_rows(TlLayerArgs a, int nblk, int tail, const TlFwdPlan& plan, hipStream_t stream) {
     constexpr int LDX = D + 4, LDH = 128 + 4;
     const size_t lds = (size_t)MR * (LDX + (LDX > LDH ? LDX : LDH)) * sizeof(float);
-    a.f.skew = tl_skew_ticks(nblk, 256 * (D <= 128 ? 2 : 1), 2000, "DTQN_SKEW_LAYER");
+    const bool head = tail == 1;
+    const bool pk = D % 128 == 0 && a.f.W1pa != nullptr && a.f.W1pb != nullptr && a.f.W2pa != nullptr && a.f.W2pb != nullptr &&
+                    a.Wopa != nullptr && a.Wopb != nullptr && (!head || (a.Wh1pa != nullptr && a.Wh1pb != nullptr)) &&
+                    (tail != 2 || (a.Winpa != nullptr && a.Winpb != nullptr));
+    a.f.skew = tl_skew_ticks(nblk, plan.slots, plan.skew_layer);
     constexpr bool CAN = D % 128 == 0;
     if (tail == 2) {
         if constexpr (CAN && MR == 64) {                               // (the projection tail exists for 64-row workgroups of d_model 128 / 256)
@@ -3539,56 +3578,44 @@ static int launch_layer_rows(TlLayerArgs a, int nblk, bool pk, int tail, hipStre
             else TL_LAUNCH((tl_layer_kernel<D, MR, false, 2>), dim3(nblk), dim3(TNT), lds, stream, a);
             return DTQN_OK;
         }
-        return DTQN_ERR_CONFIG;
+        return DTQN_ERR_CONFIG;                                        // (TlFwdPlan::qkv_fuse asks for it nowhere else)
     }
-    const bool head = tail == 1;
     if (pk && head) TL_LAUNCH((tl_layer_kernel<D, MR, CAN, 1>), dim3(nblk), dim3(TNT), lds, stream, a);
     else if (pk) TL_LAUNCH((tl_layer_kernel<D, MR, CAN, 0>), dim3(nblk), dim3(TNT), lds, stream, a);
     else if (head) TL_LAUNCH((tl_layer_kernel<D, MR, false, 1>), dim3(nblk), dim3(TNT), lds, stream, a);
     else TL_LAUNCH((tl_layer_kernel<D, MR, false, 0>), dim3(nblk), dim3(TNT), lds, stream, a);
     return DTQN_OK;
 }
-// can this launch carry the next layer's q | k | v projection? (64-row workgroups, d_model 128 / 256: launch_layer's row rule, asked in advance)
 template <int D>
-static bool layer_qkv_tail_ok(int blocks64) {
-    return D % 128 == 0 && !tl_rows32(blocks64, 256 * (D <= 128 ? 2 : 1), D, "DTQN_ROWS_FFN");
+static int launch_layer(TlLayerArgs a, int S, int tail, const TlFwdPlan& plan, hipStream_t stream) {
+    if (a.pack.L > 0 && plan.rows32_ffn) return DTQN_ERR_CONFIG;        // the plan packs only where this launch runs 64 rows
+    g_last_packed_blocks = a.pack.L > 0 ? plan.nblk_rows : 0;
+    if (a.pack.L > 0) return launch_layer_rows<D, 64>(a, plan.nblk_rows, tail, plan, stream);
+    if (!plan.rows32_ffn) return launch_layer_rows<D, 64>(a, S * a.f.rpb, tail, plan, stream);
+    a.f.rpb *= 2;
+    return launch_layer_rows<D, 32>(a, S * a.f.rpb, tail, plan, stream);
 }
-template <int D>
-static int launch_layer(TlLayerArgs a, int S, int tail, hipStream_t stream, int nblk_rows = 0) {
-    const int blocks64 = S * a.f.rpb, slots = 256 * (D <= 128 ? 2 : 1);
-    const bool head = tail == 1;
-    const bool pk = D % 128 == 0 && a.f.W1pa != nullptr && a.f.W1pb != nullptr && a.f.W2pa != nullptr && a.f.W2pb != nullptr &&
-                    a.Wopa != nullptr && a.Wopb != nullptr && (!head || (a.Wh1pa != nullptr && a.Wh1pb != nullptr)) &&
-                    (tail != 2 || (a.Winpa != nullptr && a.Winpb != nullptr));
-    if (tl_rows32(blocks64, slots, D, "DTQN_ROWS_FFN")) {
-        a.f.rpb *= 2;
-        a.pack = TlPack{0, 0, 0};
-        return launch_layer_rows<D, 32>(a, S * a.f.rpb, pk, tail, stream);
-    }
-    g_last_packed_blocks = a.pack.L > 0 && nblk_rows > 0 ? nblk_rows : 0;
-    if (a.pack.L > 0 && nblk_rows > 0) return launch_layer_rows<D, 64>(a, nblk_rows, pk, tail, stream);
-    a.pack = TlPack{0, 0, 0};
-    return launch_layer_rows<D, 64>(a, S * a.f.rpb, pk, tail, stream);
-}
-template <int KC>
-static int launch_dx(TlDxArgs a, int S, hipStream_t stream) {
-    const int cb = (a.KOUT + 16 * TNW - 1) / (16 * TNW);
-    if (a.hh.base == nullptr && tl_half_rows(S * a.rpb * cb, 512)) {
-        a.rpb *= 2;
-        const size_t lds = (size_t)32 * ((KC > 16 * TNW ? KC : 16 * TNW) + 4) * sizeof(float);   // operand tile, reused by the epilogue tile
-        if (KC == 128 && a.Wp != nullptr && a.nsrc == 1) TL_LAUNCH((tl_dx_kernel<KC, 32, KC == 128>), dim3(S * a.rpb, cb), dim3(TNT), lds, stream, a);
-        else TL_LAUNCH((tl_dx_kernel<KC, 32, false>), dim3(S * a.rpb, cb), dim3(TNT), lds, stream, a);
-    } else {
-        const size_t lds = (size_t)64 * ((KC > 16 * TNW ? KC : 16 * TNW) + 4) * sizeof(float);
+template <int KC, int MR>
+static int launch_dx_rows(const TlDxArgs& a, int S, int cb, hipStream_t stream) {
+    const size_t lds = (size_t)MR * ((KC > 16 * TNW ? KC : 16 * TNW) + 4) * sizeof(float);   // operand tile, reused by the epilogue tile
+    if constexpr (MR == 64) {
         if (a.hh.base != nullptr) {                                    // Q-head mode (64-row workgroups)
             if (KC == 128 && a.Wp != nullptr) TL_LAUNCH((tl_dx_kernel<KC, 64, KC == 128, true>), dim3(S * a.rpb, cb), dim3(TNT), lds, stream, a);
             else TL_LAUNCH((tl_dx_kernel<KC, 64, false, true>), dim3(S * a.rpb, cb), dim3(TNT), lds, stream, a);
             return DTQN_OK;
         }
-        if (KC == 128 && a.Wp != nullptr && a.nsrc == 1) TL_LAUNCH((tl_dx_kernel<KC, 64, KC == 128>), dim3(S * a.rpb, cb), dim3(TNT), lds, stream, a);
-        else TL_LAUNCH((tl_dx_kernel<KC, 64, false>), dim3(S * a.rpb, cb), dim3(TNT), lds, stream, a);
     }
+    if (KC == 128 && a.Wp != nullptr && a.nsrc == 1) TL_LAUNCH((tl_dx_kernel<KC, MR, KC == 128>), dim3(S * a.rpb, cb), dim3(TNT), lds, stream, a);
+    else TL_LAUNCH((tl_dx_kernel<KC, MR, false>), dim3(S * a.rpb, cb), dim3(TNT), lds, stream, a);
     return DTQN_OK;
+}
+// (KC <= 128: the dY W kernels count two workgroups per compute unit at every d_model)
+template <int KC>
+static int launch_dx(TlDxArgs a, int S, const TlBwdPlan& plan, hipStream_t stream) {
+    const int cb = (a.KOUT + 16 * TNW - 1) / (16 * TNW);
+    if (a.hh.base != nullptr || !tl_half_rows(plan.gemm_rows, S * a.rpb * cb, tl_slots<KC>())) return launch_dx_rows<KC, 64>(a, S, cb, stream);
+    a.rpb *= 2;
+    return launch_dx_rows<KC, 32>(a, S, cb, stream);
 }
 template <int D>
 static int launch_ln(const TlLnArgs& a, int S, hipStream_t stream) {
@@ -3605,15 +3632,9 @@ static int launch_ln_bwd(const TlLnBwdArgs& a, int S, hipStream_t stream) {
 }
 // head_dim instantiations of the attention kernels (dtqn_net_init admits exactly these on the row-block path)
 #define TL_ATTN_HEAD_DIMS(X) X(4) X(8) X(16) X(32) X(64) X(128)
-// The key-blocked kernels (tl_attn_kb_*) take over exactly where the whole-head tile does not fit LDS (dtqn_attn_whole_tile, the test
-// dtqn_net_init admits shapes by); DTQN_ATTN_KBLOCK=1 (A/B and tests, read per launch) forces them on any row-block shape.
-static inline bool tl_attn_kblock(int lpb, int HD) {
-    const char* e = getenv("DTQN_ATTN_KBLOCK");
-    return (e != nullptr && e[0] == '1') || !dtqn_attn_whole_tile(lpb, HD);
-}
-static int launch_attn(const TlAttnArgs& a, int S, int H, int HD, hipStream_t stream) {
+static int launch_attn(const TlAttnArgs& a, int S, int H, int HD, bool kblock, hipStream_t stream) {
     const size_t lds = dtqn_attn_tile_lds(a.lpb, HD, 0);
-    if (tl_attn_kblock(a.lpb, HD)) {
+    if (kblock) {
         const dim3 grid(S, H, a.lpb / TL_KB);
 #define TL_ATTN_CASE(hd)                                                                                             \
         if (HD == hd) {                                                                                              \
@@ -3635,9 +3656,9 @@ static int launch_attn(const TlAttnArgs& a, int S, int H, int HD, hipStream_t st
 #undef TL_ATTN_CASE
     return DTQN_ERR_CONFIG;
 }
-static int launch_attn_bwd(const TlAttnBwdArgs& a, int S, int H, int HD, hipStream_t stream) {
+static int launch_attn_bwd(const TlAttnBwdArgs& a, int S, int H, int HD, bool kblock, hipStream_t stream) {
     const size_t lds = dtqn_attn_tile_lds(a.lpb, HD, 1);
-    if (tl_attn_kblock(a.lpb, HD)) {        // dk | dv, then dq: both read only the forward's records and dO, and write disjoint columns
+    if (kblock) {        // dk | dv, then dq: both read only the forward's records and dO, and write disjoint columns
         const dim3 grid(S, H, a.lpb / TL_KB);
 #define TL_ATTN_CASE(hd)                                                                                             \
         if (HD == hd) {                                                                                              \
@@ -3665,16 +3686,9 @@ static int launch_attn_bwd(const TlAttnBwdArgs& a, int S, int H, int HD, hipStre
     return DTQN_ERR_CONFIG;
 }
 
-// Bag attention: the matrix-core kernels (tl_bag_attn_mfma_*) take over exactly where the resident backward's LDS request at the network's
-// full context does not fit a workgroup (dtqn_bag_attn_resident) -- by ctx_len and not by the live row count of one call, so that every
-// forward and backward of a network runs the same family; DTQN_BAG_ATTN_MFMA=1 (A/B and tests, read per launch) forces them on any bag.
-static inline bool tl_bag_mfma(const DtqnNet& net) {
-    const char* e = getenv("DTQN_BAG_ATTN_MFMA");
-    return (e != nullptr && e[0] == '1') || !dtqn_bag_attn_resident(net.ctx_len, net.bag_size, net.head_dim);
-}
-static int launch_bag_attn(const DtqnNet& net, const TlBagAttnArgs& a, int S, hipStream_t stream) {
+static int launch_bag_attn(const DtqnNet& net, const TlBagAttnArgs& a, int S, bool mfma, hipStream_t stream) {
     const int H = net.num_heads, HD = net.head_dim;
-    if (!tl_bag_mfma(net)) {
+    if (!mfma) {
         TL_LAUNCH(tl_bag_attn_kernel, dim3(S, H), dim3(256), dtqn_bag_attn_lds(0, a.bag, HD), stream, a);
         return DTQN_OK;
     }
@@ -3689,9 +3703,9 @@ static int launch_bag_attn(const DtqnNet& net, const TlBagAttnArgs& a, int S, hi
 #undef TL_ATTN_CASE
     return DTQN_ERR_CONFIG;
 }
-static int launch_bag_attn_bwd(const DtqnNet& net, const TlBagAttnBwdArgs& a, int S, hipStream_t stream) {
+static int launch_bag_attn_bwd(const DtqnNet& net, const TlBagAttnBwdArgs& a, int S, bool mfma, hipStream_t stream) {
     const int H = net.num_heads, HD = net.head_dim;
-    if (!tl_bag_mfma(net)) {
+    if (!mfma) {
         TL_LAUNCH(tl_bag_attn_bwd_kernel, dim3(S, H), dim3(256), dtqn_bag_attn_lds(a.n, a.bag, HD), stream, a);
         return DTQN_OK;
     }
@@ -3760,6 +3774,46 @@ struct EmbedSrc {
     int pre_rows = 0;
 };
 
+// Every decision of a forward pass of S sequences with n live rows (S * rpb 64-row blocks in every row launch of the pass).
+template <int D>
+static TlFwdPlan tl_fwd_plan(const DtqnNet& net, const EmbedSrc& src, int S, int n, bool training, const TlDrop& drop) {
+    TlFwdPlan p = {};
+    const int lpb = net.lp, blocks64 = S * (lpb / TROWS);
+    p.slots = tl_slots<D>();
+    // sequences the backward reads: the training third of a TD update ([0, batch) of the update = [0, batch - seq0) of this launch)
+    p.n_save = training ? (src.batch - src.seq0 > 0 ? src.batch - src.seq0 : 0) : 0;
+    p.rows32_ffn = tl_rows32(tl_sw_int<TLSW_ROWS_FFN, TLSW_FFN_ROWS>(), blocks64, p.slots, D);
+    p.rows32_wide = tl_rows32(tl_sw_int<TLSW_ROWS_WIDE, TLSW_FFN_ROWS>(), blocks64, p.slots, D);
+    p.gemm_rows = tl_gemm_rows();
+    p.no_wide = tl_sw_set<TLSW_NO_WIDE>();
+    // width-padded networks keep their LayerNorms in launches of their own (the fused epilogues take the statistics over all D columns)
+    const bool ident = net.identity != 0, gru = net.gate == DTQN_GATE_GRU, padded = net.d_real > 0;
+    // DTQN_LAYER_FUSE=0: the separate launches (out-projection + LayerNorm | feed-forward + LayerNorm | head | Q) for A/B timing and tests
+    p.fuse_tail = !gru && !ident && !padded && net.bag_size == 0 && !p.no_wide && tl_sw_int<TLSW_LAYER_FUSE>().on(true);
+    // The table embedding with layer 0's q | k | v projection in the same launch (d_model 128 / 256, post-LN: the layer reads its own input).
+    // Measured (TD-updates/s, fused | apart): config 3 (1536 workgroups, three rounds) 588 | 585; config 4 (768: a round and a half,
+    // where the projection launch has its start skew) 993 | 998; config 5 (d_model 256, 384 workgroups on 256 slots) 564 | 568.
+    // So: d_model 128 and launches of two rounds and more; DTQN_EMBED_QKV=1 forces it wherever it exists, =0 never.
+    p.embed_table_qkv = D % 128 == 0 && !ident && net.num_layers > 0 && !p.no_wide &&
+                        tl_sw_int<TLSW_EMBED_QKV>().on(D == 128 && blocks64 >= 2 * p.slots);
+    // ... and on the other layers the NEXT layer's projection in the layer launch (64-row workgroups, d_model 128 / 256; DTQN_QKV_FUSE=0: its own launch)
+    p.qkv_fuse = D % 128 == 0 && !p.rows32_ffn && !p.no_wide && tl_sw_int<TLSW_QKV_FUSE>().on(true);
+    // packed rows for the passes nobody reads again (TlPack): DTQN_PACK_ROWS=0 keeps every workgroup on (sequence, row block)
+    if (training && p.fuse_tail && S > p.n_save && drop.thresh == 0u && src.lens == nullptr && n >= 32 && n < lpb && ((long long)src.batch * n) % 64 == 0 &&
+        !p.rows32_ffn && !p.rows32_wide && (3 * D) % 128 == 0 && tl_sw_int<TLSW_PACK_ROWS>().on(true)) {
+        p.pack.n0 = p.n_save * (lpb / TROWS); p.pack.s0 = p.n_save; p.pack.L = n;
+        p.nblk_rows = p.pack.n0 + (S - p.n_save) * n / 64;
+    }
+    p.attn_kblock = tl_attn_kblock(net);
+    p.bag_mfma = net.bag_size > 0 && tl_bag_mfma(net);
+    // the kernel's own delay -- it has to be a fair share of one workgroup's run time (measured at BASELINE config 4, forward
+    // stage: the 60-us projection kernel 600; the fused layer kernel, 160 us: 0 -> 626 us, 600 -> 574, 1200 -> 558, 2400 -> 551, 4000 -> 575)
+    p.skew_ffn = tl_sw_int<TLSW_SKEW_TICKS>().or_else(600);
+    p.skew_wide = tl_sw_int<TLSW_SKEW_WIDE, TLSW_SKEW_TICKS>().or_else(600);
+    p.skew_layer = tl_sw_int<TLSW_SKEW_LAYER, TLSW_SKEW_TICKS>().or_else(2000);
+    return p;
+}
+
 // All S sequences through the network.  theta_a serves sequences [0, split), theta_b the rest.
 template <int D>
 static int forward_records(const DtqnNet& net, const float* theta_a, const float* theta_b, int split, const EmbedSrc& src,
@@ -3769,6 +3823,7 @@ static int forward_records(const DtqnNet& net, const float* theta_a, const float
     const WPackPlan wplan = (pk_a != nullptr && pk_b != nullptr) ? wpack_plan(net) : WPackPlan{};
     const int lpb = net.lp, H = net.num_heads, HD = net.head_dim, rpb = lpb / TROWS;
     const RecMap rm = rec_map(net, training);
+    const TlFwdPlan plan = tl_fwd_plan<D>(net, src, S, n, training, drop);
     bool qkv0_done = false;            // the embedding launch also ran layer 0's q | k | v projection
     const bool ident = net.identity != 0;
     int rc;
@@ -3787,21 +3842,16 @@ static int forward_records(const DtqnNet& net, const float* theta_a, const float
         if (net.img_c > 0 && e.pre == nullptr) return DTQN_ERR_ARG;     // image nets come through dtqn_img_encode
         e.ein = e.pre != nullptr ? nofld() : e.ein;
         e.ptab_a = wpack_etab(wplan, pk_a); e.ptab_b = wpack_etab(wplan, pk_b);
-        e.n_save = training ? (src.batch - src.seq0 > 0 ? src.batch - src.seq0 : 0) : 0;
+        e.n_save = plan.n_save;
         if (e.ptab_a != nullptr && e.ptab_b != nullptr && net.discrete && e.pre == nullptr) {
-            // ... with layer 0's q | k | v projection in the same launch (d_model 128 / 256, post-LN: the layer reads its own input; DTQN_EMBED_QKV=0: apart)
-            const char* eqe = getenv("DTQN_EMBED_QKV");
+            // ... with layer 0's q | k | v projection in the same launch where the plan says so (TlFwdPlan::embed_table_qkv)
             const int tb0 = net.off_layer0;
             e.qkv = F(L0(0) + net.al_qkv, 3 * D);
             e.Wina = theta_a + tb0 + net.lo_in_w; e.Winb = theta_b + tb0 + net.lo_in_w; e.bina = theta_a + tb0 + net.lo_in_b; e.binb = theta_b + tb0 + net.lo_in_b;
             e.Winpa = wpack_f(wplan, pk_a, tb0 + net.lo_in_w); e.Winpb = wpack_f(wplan, pk_b, tb0 + net.lo_in_w);
             bool with_qkv = false;
             if constexpr (D % 128 == 0) {
-                // Measured (TD-updates/s, fused | apart): config 3 (1536 workgroups, three rounds) 588 | 585; config 4 (768: a round and a half,
-                // where the projection launch has its start skew) 993 | 998; config 5 (d_model 256, 384 workgroups on 256 slots) 564 | 568.
-                // So: d_model 128 and launches of two rounds and more; DTQN_EMBED_QKV=1 forces it wherever it exists, =0 never.
-                const bool pays = D == 128 && S * rpb >= 2 * 512;
-                if (!ident && net.num_layers > 0 && getenv("DTQN_NO_WIDE") == nullptr && (eqe != nullptr ? atoi(eqe) != 0 : pays)) {
+                if (plan.embed_table_qkv) {
                     const size_t lds = ((size_t)TROWS * ((D + 4) + (128 + 4))) * sizeof(float) + (size_t)TROWS * net.obs_dim * sizeof(int);
                     if (e.Winpa != nullptr && e.Winpb != nullptr) TL_LAUNCH((tl_embed_table_kernel<D, true>), dim3(S * rpb), dim3(TNT), lds, stream, e);
                     else TL_LAUNCH((tl_embed_table_kernel<D, false>), dim3(S * rpb), dim3(TNT), lds, stream, e);
@@ -3821,7 +3871,7 @@ static int forward_records(const DtqnNet& net, const float* theta_a, const float
         a.Wa = theta_a + w_off; a.Wb = theta_b + w_off; a.ba = theta_a + b_off; a.bb = theta_b + b_off;
         a.split = split; a.K = K; a.N = N; a.rpb = rpb; a.mode = mode;
         a.Wpa = wpack_f(wplan, pk_a, w_off); a.Wpb = wpack_f(wplan, pk_b, w_off);
-        return launch_linear<D>(a, S, stream);
+        return launch_linear<D>(a, S, plan, stream);
     };
     // out = GRUGate(x, y) (gates.py:26-31): three two-operand GEMMs with the gate arithmetic as their epilogues.
     // grec: the gate's record (z, r, h~, r*x, x, y), y already in place.
@@ -3839,14 +3889,14 @@ static int forward_records(const DtqnNet& net, const float* theta_a, const float
         };
         TlLinearArgs a = pair(x, net.go_w_r, net.go_u_r, -1);
         a.mode = 3; a.out = r; a.out2 = rx; a.out3 = training ? F(grec + 4 * LPD, D) : nofld();
-        int rc2 = launch_linear<D>(a, S, stream);
+        int rc2 = launch_linear<D>(a, S, plan, stream);
         if (rc2 != DTQN_OK) return rc2;
         a = pair(x, net.go_w_z, net.go_u_z, net.go_b_z);
         a.mode = 3; a.out = z;
-        if ((rc2 = launch_linear<D>(a, S, stream)) != DTQN_OK) return rc2;
+        if ((rc2 = launch_linear<D>(a, S, plan, stream)) != DTQN_OK) return rc2;
         a = pair(rx, net.go_w_g, net.go_u_g, -1);
         a.mode = 4; a.out = h; a.aux = z; a.out2 = out;
-        return launch_linear<D>(a, S, stream);
+        return launch_linear<D>(a, S, plan, stream);
     };
     auto lnorm = [&](Fld s_, Fld d_, Fld st, int w_off, int b_off) {
         TlLnArgs a;
@@ -3855,26 +3905,9 @@ static int forward_records(const DtqnNet& net, const float* theta_a, const float
         a.split = split; a.rpb = rpb; a.d_real = net.d_real;
         return launch_ln<D>(a, S, stream);
     };
-    // width-padded networks keep their LayerNorms in launches of their own (the fused epilogues below take the statistics over all D columns)
-    const bool padded = net.d_real > 0;
-    // DTQN_LAYER_FUSE=0: the separate launches (out-projection + LayerNorm | feed-forward + LayerNorm | head | Q) for A/B timing and tests
-    const char* lfe = getenv("DTQN_LAYER_FUSE");
-    const bool fuse_tail = !gru && !ident && !padded && net.bag_size == 0 && getenv("DTQN_NO_WIDE") == nullptr && (lfe == nullptr || atoi(lfe) != 0);
+    const bool padded = net.d_real > 0;           // (width-padded networks keep their LayerNorms in launches of their own)
     bool head_done = false;
     int qkv_done_for = qkv0_done ? 0 : -1;
-    // sequences the backward reads: the training third of a TD update ([0, batch) of the update = [0, batch - seq0) of this launch)
-    const int n_save = training ? (src.batch - src.seq0 > 0 ? src.batch - src.seq0 : 0) : 0;
-    // packed rows for the rest (TlPack): DTQN_PACK_ROWS=0 keeps every workgroup on (sequence, row block)
-    TlPack pack = {0, 0, 0};
-    {
-        const char* pe = getenv("DTQN_PACK_ROWS");
-        const bool rows64 = !tl_rows32(S * rpb, 256 * (D <= 128 ? 2 : 1), D, "DTQN_ROWS_FFN") && !tl_rows32(S * rpb, 256 * (D <= 128 ? 2 : 1), D, "DTQN_ROWS_WIDE");
-        if (training && fuse_tail && S > n_save && drop.thresh == 0u && src.lens == nullptr && n >= 32 && n < lpb && ((long long)src.batch * n) % 64 == 0 &&
-            rows64 && (3 * D) % 128 == 0 && (pe == nullptr || atoi(pe) != 0)) {
-            pack.n0 = n_save * rpb; pack.s0 = n_save; pack.L = n;
-        }
-    }
-    const int nblk_rows = pack.L > 0 ? pack.n0 + (S - n_save) * n / 64 : 0;      // workgroups of a packed launch
     for (int l = 0; l < net.num_layers; ++l) {
         const int tb = net.off_layer0 + l * net.layer_stride, ab = L0(l);
         const bool last = l + 1 == net.num_layers;
@@ -3885,14 +3918,14 @@ static int forward_records(const DtqnNet& net, const float* theta_a, const float
         if (ident && (rc = lnorm(stream_in, u1, st1, tb + net.lo_ln1_w, tb + net.lo_ln1_b)) != DTQN_OK) return rc;
         if (qkv_done_for == l) {
             rc = DTQN_OK;                                                      // the previous layer's fused launch wrote this layer's q | k | v
-        } else if ((3 * D) % 128 == 0 && getenv("DTQN_NO_WIDE") == nullptr) {  // packed q | k | v projection: one workgroup per row block walks the column blocks
+        } else if ((3 * D) % 128 == 0 && !plan.no_wide) {                       // packed q | k | v projection: one workgroup per row block walks the column blocks
             TlWideArgs wa = {};
             wa.in = u1; wa.out = F(ab + net.al_qkv, 3 * D);
             wa.Wa = theta_a + tb + net.lo_in_w; wa.Wb = theta_b + tb + net.lo_in_w; wa.ba = theta_a + tb + net.lo_in_b; wa.bb = theta_b + tb + net.lo_in_b;
             wa.split = split; wa.rpb = rpb; wa.N = 3 * D;
             wa.Wpa = wpack_f(wplan, pk_a, tb + net.lo_in_w); wa.Wpb = wpack_f(wplan, pk_b, tb + net.lo_in_w);
-            wa.pack = pack;
-            rc = launch_wide<D>(wa, S, stream, nblk_rows);
+            wa.pack = plan.pack;
+            rc = launch_wide<D>(wa, S, plan, stream);
         } else {
             rc = linear(u1, D, 3 * D, tb + net.lo_in_w, tb + net.lo_in_b, F(ab + net.al_qkv, 3 * D), 0, nofld(), nofld());
         }
@@ -3903,10 +3936,10 @@ static int forward_records(const DtqnNet& net, const float* theta_a, const float
             at.lse = training ? F(ab + net.al_lse, lpb) : nofld();
             at.D = D; at.lpb = lpb; at.n = n; at.drop = drop; at.layer = l;
             at.hd_eff = (float)(net.hd_real > 0 ? net.hd_real : HD);
-            if ((rc = launch_attn(at, S, H, HD, stream)) != DTQN_OK) return rc;
+            if ((rc = launch_attn(at, S, H, HD, plan.attn_kblock, stream)) != DTQN_OK) return rc;
         }
         // post-LN residual layer: everything behind the attention in ONE launch (tl_layer_kernel), with the Q head on the last layer
-        if (fuse_tail) {
+        if (plan.fuse_tail) {
             TlLayerArgs la = {};
             la.o = F(ab + net.al_o, D); la.res = stream_in; la.s1 = s1; la.u2 = u2;
             la.m1 = training ? F(ab + net.al_m1, 0) : nofld(); la.st1 = st1;
@@ -3919,8 +3952,8 @@ static int forward_records(const DtqnNet& net, const float* theta_a, const float
             fa.split = split; fa.rpb = rpb; fa.drop = drop; fa.layer = l;
             fa.W1pa = wpack_f(wplan, pk_a, tb + net.lo_f1_w); fa.W1pb = wpack_f(wplan, pk_b, tb + net.lo_f1_w);
             fa.W2pa = wpack_f(wplan, pk_a, tb + net.lo_f2_w); fa.W2pb = wpack_f(wplan, pk_b, tb + net.lo_f2_w);
-            fa.n_save = n_save;
-            la.pack = pack;
+            fa.n_save = plan.n_save;
+            la.pack = plan.pack;
             fa.h = training ? F(ab + net.al_h, 4 * D) : nofld();
             fa.mh = training ? F(ab + net.al_mh, 0) : nofld();
             fa.m2 = training ? F(ab + net.al_m2, 0) : nofld();
@@ -3938,9 +3971,8 @@ static int forward_records(const DtqnNet& net, const float* theta_a, const float
                 la.q = q_out; la.q_seq_stride = q_seq_stride; la.q_row_stride = q_row_stride; la.A = net.num_actions; la.n = n;
                 head_done = true;
             }
-            // ... or, on the other layers of d_model 128 / 256, the NEXT layer's q | k | v projection (DTQN_QKV_FUSE=0: its own launch)
-            const char* qfe = getenv("DTQN_QKV_FUSE");
-            const bool qkv_next = !last && layer_qkv_tail_ok<D>(S * rpb) && getenv("DTQN_NO_WIDE") == nullptr && (qfe == nullptr || atoi(qfe) != 0);
+            // ... or, on the other layers, the NEXT layer's q | k | v projection (TlFwdPlan::qkv_fuse)
+            const bool qkv_next = !last && plan.qkv_fuse;
             if (qkv_next) {
                 const int tbn = net.off_layer0 + (l + 1) * net.layer_stride;
                 la.qkv = F(L0(l + 1) + net.al_qkv, 3 * D);
@@ -3948,11 +3980,11 @@ static int forward_records(const DtqnNet& net, const float* theta_a, const float
                 la.Winpa = wpack_f(wplan, pk_a, tbn + net.lo_in_w); la.Winpb = wpack_f(wplan, pk_b, tbn + net.lo_in_w);
                 qkv_done_for = l + 1;
             }
-            if ((rc = launch_layer<D>(la, S, head ? 1 : (qkv_next ? 2 : 0), stream, nblk_rows)) != DTQN_OK) return rc;
+            if ((rc = launch_layer<D>(la, S, head ? 1 : (qkv_next ? 2 : 0), plan, stream)) != DTQN_OK) return rc;
             continue;
         }
         // s1 = gate(stream, relu(o W_o^T + b)), then the LayerNorm behind it
-        if (!gru && !ident && !padded && getenv("DTQN_NO_WIDE") == nullptr) {
+        if (!gru && !ident && !padded && !plan.no_wide) {
             // post-LN residual layer: out-projection, residual add and LayerNorm-1 in one launch (s1 kept for the backward only)
             TlWideArgs wa = {};
             wa.in = F(ab + net.al_o, D); wa.out = s1; wa.N = D;
@@ -3962,8 +3994,8 @@ static int forward_records(const DtqnNet& net, const float* theta_a, const float
             wa.res = stream_in; wa.mask = training ? F(ab + net.al_m1, 0) : nofld();
             wa.ln_out = u2; wa.ln_st = st1;
             wa.lga = theta_a + tb + net.lo_ln1_w; wa.lgb = theta_b + tb + net.lo_ln1_w; wa.lba = theta_a + tb + net.lo_ln1_b; wa.lbb = theta_b + tb + net.lo_ln1_b;
-            wa.n_save = n_save;
-            if ((rc = launch_wide<D>(wa, S, stream)) != DTQN_OK) return rc;
+            wa.n_save = plan.n_save;
+            if ((rc = launch_wide<D>(wa, S, plan, stream)) != DTQN_OK) return rc;
         } else {
             if (!gru) {
                 rc = linear(F(ab + net.al_o, D), D, D, tb + net.lo_out_w, tb + net.lo_out_b, s1, 2, stream_in,
@@ -3988,7 +4020,7 @@ static int forward_records(const DtqnNet& net, const float* theta_a, const float
             fa.split = split; fa.rpb = rpb; fa.drop = drop; fa.layer = l;
             fa.W1pa = wpack_f(wplan, pk_a, tb + net.lo_f1_w); fa.W1pb = wpack_f(wplan, pk_b, tb + net.lo_f1_w);
             fa.W2pa = wpack_f(wplan, pk_a, tb + net.lo_f2_w); fa.W2pb = wpack_f(wplan, pk_b, tb + net.lo_f2_w);
-            fa.n_save = n_save;                                       // only the training third of a TD update is read again
+            fa.n_save = plan.n_save;                                  // only the training third of a TD update is read again
             fa.h = training ? F(ab + net.al_h, 4 * D) : nofld();
             fa.mh = training ? F(ab + net.al_mh, 0) : nofld();
             fa.m2 = training ? F(ab + net.al_m2, 0) : nofld();
@@ -4001,7 +4033,7 @@ static int forward_records(const DtqnNet& net, const float* theta_a, const float
                 fa.lga = theta_a + tb + net.lo_ln2_w; fa.lgb = theta_b + tb + net.lo_ln2_w;
                 fa.lba = theta_a + tb + net.lo_ln2_b; fa.lbb = theta_b + tb + net.lo_ln2_b;
             }
-            rc = launch_ffn<D>(fa, S, stream);
+            rc = launch_ffn<D>(fa, S, plan, stream);
             if (rc == DTQN_OK && gru) rc = gate(ident ? s1 : u2, ab + net.al_gate2, net.off_gate_mlp, s2);
         }
         if (rc != DTQN_OK) return rc;
@@ -4044,7 +4076,7 @@ static int forward_records(const DtqnNet& net, const float* theta_a, const float
             at.q = F(rm.bag_q, D); at.kv = F(rm.bag_kv, 2 * D); at.o = F(rm.bag_o, D);
             at.p = training ? F(net.ao_bag_p, net.bag_ld) : nofld();
             at.D = D; at.HD = HD; at.n = n; at.bag = bag; at.bag_ld = net.bag_ld; at.lpb = lpb; at.drop = drop;
-            if ((rc = launch_bag_attn(net, at, S, stream)) != DTQN_OK) return rc;
+            if ((rc = launch_bag_attn(net, at, S, plan.bag_mfma, stream)) != DTQN_OK) return rc;
         }
         if ((rc = linear(F(rm.bag_o, D), D, D, net.off_bag_out_w, net.off_bag_out_b, F(rm.xcat + D, 2 * D), 0, nofld(), nofld())) != DTQN_OK) return rc;
         if ((rc = linear(xw, 2 * D, D, net.off_head1_w, net.off_head1_b, F(rm.hh, D), 1, nofld(), nofld())) != DTQN_OK) return rc;
@@ -4072,6 +4104,30 @@ struct BwdIn {
     TlDrop drop;                       // the keep masks of the forward the records came from
 };
 
+// Every decision of a backward pass over B sequences (B * rpb 64-row blocks in every row launch of the pass).
+template <int D>
+static TlBwdPlan tl_bwd_plan(const DtqnNet& net, int B, const DtqnTd& td) {
+    TlBwdPlan p = {};
+    const bool ident = net.identity != 0, gru = net.gate == DTQN_GATE_GRU;
+    // the VALU half of the Q-head backward rides in the staging of the dL/dxf product (TlDxArgs, Q-head mode); with a bag the head's
+    // input is [working memory | persistent memory] and the separate launch stays.  DTQN_HEAD_FUSE=0: the separate launch (A/B, tests)
+    p.head_fuse = net.bag_size == 0 && tl_sw_int<TLSW_HEAD_FUSE>().on(true);
+    p.rows32_ffnb = tl_rows32(tl_sw_int<TLSW_ROWS_FFNB, TLSW_FFN_ROWS>(), B * (net.lp / TROWS), tl_slots<D>(), D);
+    p.gemm_rows = tl_gemm_rows();
+    // the fused feed-forward backward: D <= 128 only: measured cfg 4 825 -> 838 updates/s, but cfg 5 (D = 256: 172 registers, one
+    // workgroup per CU) 461 -> 458
+    p.ffn_bwd = tl_sw_int<TLSW_FFN_BWD>().on(D <= 128);
+    // DTQN_BWD_CHAIN=0: the separate launches (A/B timing, tests).  64-row workgroups only: the LayerNorm column partials are per 64-row block.
+    // d_model 256 (one workgroup per compute unit): only beside a second stream (DtqnTd.side_stream; DTQN_BWD_CHAIN256=0|1 forces).  Measured at
+    // BASELINE config 5 (32 sequences = 128 64-row workgroups on 256 compute units): alone the chain is slower than the 32-row separate launches
+    // (backward stage 633 against 583 us), with the next update's target pass running on the other half of the chip it wins (522 -> 552 updates/s)
+    p.chain = !gru && !ident && net.d_real == 0 && tl_sw_int<TLSW_BWD_CHAIN>().on(true) &&
+              (D <= 128 ? p.ffn_bwd && !p.rows32_ffnb : tl_sw_int<TLSW_BWD_CHAIN256>().on(td.side_stream != 0));
+    p.attn_kblock = tl_attn_kblock(net);
+    p.bag_mfma = net.bag_size > 0 && tl_bag_mfma(net);
+    return p;
+}
+
 // Data-gradient chain of the B TRAIN sequences (records [0, B) of td->act), residual gate; post-LN (transformer.py:63-78)
 // or identity-reordered (transformer.py:86-101) layers.
 // The gradient of the residual stream lives in grd.go_dx0 throughout (it IS dL/dx0 at the end).
@@ -4082,6 +4138,7 @@ static int backward_records(const DtqnNet& net, const BwdIn& in, const DtqnTd& t
     const float* theta = td.theta_pol;
     float* act = td.act;
     float* grd = td.grd;
+    const TlBwdPlan plan = tl_bwd_plan<D>(net, B, td);
     int rc;
     auto FA = [&](int off, int ld) { return fld(act, net.act_stride, off, ld); };
     auto FG = [&](int off, int ld) { return fld(grd, net.grd_stride, off, ld); };
@@ -4098,11 +4155,8 @@ static int backward_records(const DtqnNet& net, const BwdIn& in, const DtqnTd& t
         a.ep_idx = td.ep_idx; a.start = td.start; a.batch = B; a.history = td.history; a.gamma = td.gamma;
         TL_LAUNCH(tl_loss_kernel, dim3(B), dim3(256), 0, stream, a);
     }
-    // the VALU half of the Q-head backward rides in the staging of the dL/dxf product below (TlDxArgs, Q-head mode); with a bag the head's
-    // input is [working memory | persistent memory] and the separate launch stays.  DTQN_HEAD_FUSE=0: the separate launch (A/B, tests)
-    const char* hfe = getenv("DTQN_HEAD_FUSE");
-    const bool head_fused = net.bag_size == 0 && (hfe == nullptr || atoi(hfe) != 0);
-    if (!head_fused) {
+    // the Q-head backward: inside the dL/dxf product below (TlBwdPlan::head_fuse), or its own launch
+    if (!plan.head_fuse) {
         TlHeadBwdArgs a;
         a.hh = FA(net.ao_hh, D); a.dq = FG(net.go_dq, net.ap); a.dhh = FG(net.go_dhh, D);
         a.W2 = theta + net.off_head2_w; a.D = D; a.A = net.num_actions; a.rpb = rpb;
@@ -4113,7 +4167,7 @@ static int backward_records(const DtqnNet& net, const BwdIn& in, const DtqnTd& t
         TlDxArgs a = {};
         a.dy = dy; a.out = out; a.mask = mask; a.W = theta + w_off; a.N = N; a.KOUT = KOUT; a.rpb = rpb; a.mode = mode; a.nsrc = 1;
         a.Wp = wpack_b(wplan, pk, w_off);
-        return launch_dx<KC>(a, B, stream);
+        return launch_dx<KC>(a, B, plan, stream);
     };
     auto ln_bwd = [&](Fld dy, Fld xin, Fld st, int gamma_off, int dgb_off, bool accumulate) {
         TlLnBwdArgs a;
@@ -4155,10 +4209,10 @@ static int backward_records(const DtqnNet& net, const BwdIn& in, const DtqnTd& t
         a.N = D; a.KOUT = D; a.rpb = rpb;
         a.dy = dz; a.W = theta + gw + net.go_u_z; a.dy2 = dr; a.W2 = theta + gw + net.go_u_r; a.nsrc = 2;
         a.out = G; a.mode = 2;                                                        // dx += dz_pre U_z + dr_pre U_r
-        if ((rc2 = launch_dx<KC>(a, B, stream)) != DTQN_OK) return rc2;
+        if ((rc2 = launch_dx<KC>(a, B, plan, stream)) != DTQN_OK) return rc2;
         a.dy = dh; a.W = theta + gw + net.go_w_g; a.dy2 = dz; a.W2 = theta + gw + net.go_w_z; a.dy3 = dr; a.W3 = theta + gw + net.go_w_r;
         a.nsrc = 3; a.out = dst; a.mode = 1; a.mask = m;                              // dy, through the ReLU of the sub-layer output
-        return launch_dx<KC>(a, B, stream);
+        return launch_dx<KC>(a, B, plan, stream);
     };
     if (net.bag_size > 0) {
         // d xcat = dhh W_1 ([D][2D]); its left half is dL/d(working memory) so far, its right half dL/d(persistent memory)
@@ -4176,34 +4230,24 @@ static int backward_records(const DtqnNet& net, const BwdIn& in, const DtqnTd& t
             at.q = FA(net.ao_bag_q, D); at.kv = FA(net.ao_bag_kv, 2 * D); at.p = FA(net.ao_bag_p, net.bag_ld); at.dO = FG(net.go_bag_do, D);
             at.o = FA(net.ao_bag_o, D); at.dq = FG(net.go_bag_dq, D); at.dkv = FG(net.go_bag_dkv, 2 * D);
             at.D = D; at.HD = HD; at.n = L; at.bag = bag; at.bag_ld = net.bag_ld; at.lpb = lpb; at.drop = drop;
-            if ((rc = launch_bag_attn_bwd(net, at, B, stream)) != DTQN_OK) return rc;
+            if ((rc = launch_bag_attn_bwd(net, at, B, plan.bag_mfma, stream)) != DTQN_OK) return rc;
         }
         if ((rc = dx(FG(net.go_bag_dq, D), D, net.off_bag_in_w, D, G, 2, nofld())) != DTQN_OK) return rc;                  // + dq W_q
         if ((rc = dx(FG(net.go_bag_dkv, 2 * D), 2 * D, net.off_bag_in_w + D * D, D, FG(net.go_bag_de, D), 0, nofld())) != DTQN_OK) return rc;   // d E_bag
     } else
-    if (head_fused) {
+    if (plan.head_fuse) {
         TlDxArgs a = {};
         a.dy = FG(net.go_dhh, D); a.out = G; a.W = theta + net.off_head1_w; a.N = D; a.KOUT = D; a.rpb = rpb; a.mode = 0; a.nsrc = 1;
         a.Wp = wpack_b(wplan, pk, net.off_head1_w);
         a.hh = FA(net.ao_hh, D); a.dq = FG(net.go_dq, net.ap); a.Wq = theta + net.off_head2_w; a.A = net.num_actions;
-        if ((rc = launch_dx<KC>(a, B, stream)) != DTQN_OK) return rc;                                    // dhh and dL/dxf
+        if ((rc = launch_dx<KC>(a, B, plan, stream)) != DTQN_OK) return rc;                                    // dhh and dL/dxf
     } else
     if ((rc = dx(FG(net.go_dhh, D), D, net.off_head1_w, D, G, 0, nofld())) != DTQN_OK) return rc;       // dL/dxf
-    // DTQN_BWD_CHAIN=0: the separate launches (A/B timing, tests).  64-row workgroups only: the LayerNorm column partials are per 64-row block
-    const char* bce = getenv("DTQN_BWD_CHAIN");
-    const char* ffb0 = getenv("DTQN_FFN_BWD");
-    // d_model 256 (one workgroup per compute unit): only beside a second stream (DtqnTd.side_stream; DTQN_BWD_CHAIN256=0|1 forces).  Measured at
-    // BASELINE config 5 (32 sequences = 128 64-row workgroups on 256 compute units): alone the chain is slower than the 32-row separate launches
-    // (backward stage 633 against 583 us), with the next update's target pass running on the other half of the chip it wins (522 -> 552 updates/s)
-    const char* bc256 = getenv("DTQN_BWD_CHAIN256");
-    const bool chain = !gru && !ident && net.d_real == 0 && (bce == nullptr || atoi(bce) != 0) &&
-                       (D <= 128 ? (ffb0 == nullptr || atoi(ffb0) != 0) && !tl_rows32(B * rpb, 256 * 2, D, "DTQN_ROWS_FFNB")
-                                 : (bc256 != nullptr ? atoi(bc256) != 0 : td.side_stream != 0));
     for (int l = net.num_layers - 1; l >= 0; --l) {
         const int tb = net.off_layer0 + l * net.layer_stride;
         const int ab = net.ao_layer0 + l * net.act_layer_stride, gb = net.go_layer0 + l * net.grd_layer_stride;
         const int sm = net.so_ln + l * 4 * D;
-        if (chain) {
+        if (plan.chain) {
             // post-LN residual layer: LN2', the feed-forward block, LN1', the gate mask and dO = da W_o in one launch (tl_chain_bwd_kernel)
             TlChainBwdArgs c = {};
             c.f.dy = G; c.f.out = G; c.f.out_mode = 2; c.f.m2 = FA(ab + net.al_m2, 0); c.f.df = FG(gb + net.gl_df, D);
@@ -4220,10 +4264,9 @@ static int backward_records(const DtqnNet& net, const BwdIn& in, const DtqnTd& t
         // post-LN: x_out = LN2(s2)
         if (!ident && (rc = ln_bwd(G, FA(ab + net.al_s2, D), FA(ab + net.al_st2, 2), tb + net.lo_ln2_w, sm + 2 * D, false)) != DTQN_OK) return rc;
         // s2 = (u2 | s1) + relu(f):  df = ds2 * [f > 0];  dh' = (df W2) * [h > 0];  du2 = dh' W1
-        // one fused launch: the gate's ReLU mask (residual gate) rides in its staging, dh' is written once and never read back.
-        // D <= 128 only: measured cfg 4 825 -> 838 updates/s, but cfg 5 (D = 256: 172 registers, one workgroup per CU) 461 -> 458
-        const char* ffb = getenv("DTQN_FFN_BWD");
-        if (ffb != nullptr ? atoi(ffb) != 0 : D <= 128) {
+        // one fused launch: the gate's ReLU mask (residual gate) rides in its staging, dh' is written once and never read back
+        // (TlBwdPlan::ffn_bwd)
+        if (plan.ffn_bwd) {
             TlFfnBwdArgs fb = {};
             if (!gru) { fb.dy = G; fb.m2 = FA(ab + net.al_m2, 0); fb.df = FG(gb + net.gl_df, D); }
             else {
@@ -4235,7 +4278,7 @@ static int backward_records(const DtqnNet& net, const BwdIn& in, const DtqnTd& t
             fb.W1 = theta + tb + net.lo_f1_w; fb.W2 = theta + tb + net.lo_f2_w; fb.rpb = rpb; fb.drop = drop; fb.layer = l;
             fb.W1p = wpack_b(wplan, pk, tb + net.lo_f1_w); fb.W2p = wpack_b(wplan, pk, tb + net.lo_f2_w);
             if (!ident) { fb.out = G; fb.out_mode = 2; } else { fb.out = T; fb.out_mode = 0; }
-            if ((rc = launch_ffn_bwd<D>(fb, B, stream)) != DTQN_OK) return rc;
+            if ((rc = launch_ffn_bwd<D>(fb, B, plan, stream)) != DTQN_OK) return rc;
             if (!ident) {
                 if ((rc = ln_bwd(G, FA(ab + net.al_s1, D), FA(ab + net.al_st1, 2), tb + net.lo_ln1_w, sm, false)) != DTQN_OK) return rc;
             } else {
@@ -4265,7 +4308,7 @@ static int backward_records(const DtqnNet& net, const BwdIn& in, const DtqnTd& t
             a.dO = FG(net.go_do, D); a.dqkv = FG(gb + net.gl_dqkv, 3 * D);
             a.D = D; a.lpb = lpb; a.n = L; a.drop = drop; a.layer = l;
             a.hd_eff = (float)(net.hd_real > 0 ? net.hd_real : HD);
-            if ((rc = launch_attn_bwd(a, B, H, HD, stream)) != DTQN_OK) return rc;
+            if ((rc = launch_attn_bwd(a, B, H, HD, plan.attn_kblock, stream)) != DTQN_OK) return rc;
         }
         if (!ident) {
             if ((rc = dx(FG(gb + net.gl_dqkv, 3 * D), 3 * D, tb + net.lo_in_w, D, G, 2, nofld())) != DTQN_OK) return rc;

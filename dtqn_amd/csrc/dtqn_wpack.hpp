@@ -13,8 +13,8 @@
 // whoever wrote theta in between (Adam, a hard target sync, load_state_dict).  Networks the plan does not cover (d_model not a
 // multiple of 128, bag networks) and callers that leave DtqnTd.wpack_* NULL run on the parameter layout as before.
 #pragma once
-#include <cstdlib>
 #include "dtqn_hip.h"
+#include "dtqn_tl_switch.hpp"
 
 namespace dtqn {
 
@@ -43,8 +43,7 @@ static inline int wpack_etab_floats(const DtqnNet& net) {
 }
 static inline WPackPlan wpack_plan(const DtqnNet& net) {
     WPackPlan p = {};
-    const char* e = getenv("DTQN_WPACK");
-    if (!net.tiled || net.d_model % 128 != 0 || net.bag_size > 0 || net.num_layers > 8 || (e != nullptr && atoi(e) == 0)) return p;
+    if (!net.tiled || net.d_model % 128 != 0 || net.bag_size > 0 || net.num_layers > 8 || !tl_sw_int<TLSW_WPACK>().on(true)) return p;
     const int D = net.d_model;
     auto add = [&](int w_off, int N, int K) {
         WPackMat& m = p.m[p.n++];
@@ -61,8 +60,7 @@ static inline WPackPlan wpack_plan(const DtqnNet& net) {
     add(net.off_head1_w, D, D);
     for (int j = 0; j < p.n; ++j) p.m[j].b_off = p.f_total + p.m[j].f_off;
     p.total = 2 * p.f_total;
-    const char* ee = getenv("DTQN_EMBED_TABLE");
-    p.e_floats = (ee != nullptr && atoi(ee) == 0) ? 0 : wpack_etab_floats(net);
+    p.e_floats = tl_sw_int<TLSW_EMBED_TABLE>().on(true) ? wpack_etab_floats(net) : 0;
     p.e_off = p.total;
     p.total += p.e_floats;
     return p;
