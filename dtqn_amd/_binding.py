@@ -169,6 +169,9 @@ def load_library(path: str) -> ctypes.CDLL:
     return lib
 
 
+# bounds of a discrete observation, read from dtqn_limits.h (named by make_net when it refuses one)
+_LIMITS = parse_defines(os.path.join(REPO, "dtqn_amd", "csrc", "dtqn_limits.h"))
+DISCRETE_LIMITS = (_LIMITS["DTQN_MAX_OBS_TOKENS"], _LIMITS["DTQN_MAX_EMBED_COLS"], _LIMITS["DTQN_MAX_TABLE_FLOATS"])
 GATES = {"res": DEFINES["DTQN_GATE_RES"], "gru": DEFINES["DTQN_GATE_GRU"]}
 POS = {"learned": DEFINES["DTQN_POS_LEARNED"], "sin": DEFINES["DTQN_POS_SIN"], "none": DEFINES["DTQN_POS_NONE"]}
 
@@ -192,9 +195,14 @@ def make_net(lib, *, obs_dim, num_actions, embed_per_obs_dim=8, action_dim=0, in
         net.obs_dim = net.img_c * net.img_h * net.img_w
     rc = lib.dtqn_net_init(ctypes.byref(net))
     if rc != 0:
+        why = ""
+        if discrete and image is None:
+            tok, cols, tab = DISCRETE_LIMITS
+            why = (f"; discrete observations: obs_dim {net.obs_dim} <= {tok}, obs_dim * embed_per_obs {net.obs_dim * net.embed_per_obs} <= {cols}, "
+                   f"vocab * embed_per_obs {net.vocab * net.embed_per_obs} <= {tab}, and at d_model 16 / 32 obs_dim * embed_per_obs <= 3 * d_model")
         raise NotImplementedError(
             f"dtqn_net_init rc={rc}: this DTQN variant/shape is outside the gfx950 kernels' coverage "
-            f"(D={inner_embed_size}, H={num_heads}, L={history_len}, gate={gate}, dropout={dropout}, bag_size={bag_size}); see DESIGN.md")
+            f"(D={inner_embed_size}, H={num_heads}, L={history_len}, gate={gate}, dropout={dropout}, bag_size={bag_size}{why}); see DESIGN.md")
     return net
 
 

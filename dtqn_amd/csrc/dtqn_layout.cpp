@@ -66,6 +66,9 @@ extern "C" int dtqn_net_init(DtqnNet* net) {
     const int D = net->d_model, H = net->num_heads;
     if (D % 16 != 0 || D % H != 0) return DTQN_ERR_CONFIG;
     if (net->discrete && (V < 1 || e < 1)) return DTQN_ERR_CONFIG;
+    // discrete observations: as many tokens, gathered columns and table floats as every embedding launch has LDS for (dtqn_limits.h)
+    if (net->discrete && (O > DTQN_MAX_OBS_TOKENS || (long long)O * e > DTQN_MAX_EMBED_COLS || (long long)V * e > DTQN_MAX_TABLE_FLOATS))
+        return DTQN_ERR_CONFIG;
     if (net->gate != DTQN_GATE_RES && net->gate != DTQN_GATE_GRU) return DTQN_ERR_CONFIG;
     if (net->pos < DTQN_POS_LEARNED || net->pos > DTQN_POS_NONE) return DTQN_ERR_CONFIG;
     if (!(net->dropout >= 0.f && net->dropout < 1.f)) return DTQN_ERR_CONFIG;
@@ -122,6 +125,14 @@ extern "C" int dtqn_net_init(DtqnNet* net) {
             net->lp = (L + 63) / 64 * 64;
         }
     }
+    if (!net->tiled && net->discrete && net->kep > 3 * D && (D == 64 || D == 128 || D == 256)) {
+        // an observation whose embedding operands exceed the whole-sequence kernels' LDS tile: the row-block kernels take any admitted width
+        net->tiled = 1;
+        net->lp = (L + 63) / 64 * 64;
+    }
+    // the row-block embedding gradient: the resident kernel, or the panel kernel inside a workgroup's 160 KB (action_dim is its only open term).
+    // Whatever the family: a whole-sequence network's backward with a caller's dL/dQ runs on its row-block twin
+    if (net->discrete && !dtqn_embed_bwd_resident(1, a, O, V, e) && dtqn_embed_bwd_panel_lds(a, O) > 160 * 1024) return DTQN_ERR_CONFIG;
     const int LP = net->lp;
     // the bag branch is composed from the row-block kernels: as many bag entries as the records have rows
     if (net->bag_size > 0 && (net->bag_size > LP || !(D == 64 || D == 128 || D == 256))) return DTQN_ERR_CONFIG;

@@ -24,6 +24,44 @@ static inline int dtqn_attn_whole_tile(int lp, int hd) { return dtqn_attn_tile_l
 static inline size_t dtqn_bag_attn_lds(int n, int bag, int hd) { return ((size_t)2 * bag * hd + (size_t)n * bag) * sizeof(float); }
 static inline int dtqn_bag_attn_resident(int ctx, int bag, int hd) { return dtqn_bag_attn_lds(ctx, bag, hd) <= 160 * 1024; }
 
+// Discrete observations (Embedding -> Flatten -> Linear(obs_dim * e, d), representations.py:25-52): what dtqn_net_init admits.  Every
+// embedding launch of the row-block path fits the 160 KB of a workgroup inside these bounds at d_model 64 / 128 / 256 (bytes at the bounds,
+// d_model 256, the largest):  tl_embed_kernel 132 096 (tl_embed_lds: the [64 + D][68] operand chunks, 64 x obs_dim tokens, the column map
+// and a table of at most 2048 floats);  tl_embed_table_kernel 133 120 ([64][D + 4] + [64][132] tiles and the tokens);
+// tl_embed_bwd_panel_kernel 132 368 + 256 (action_dim + 1) (dtqn_embed_bwd_panel_lds; dtqn_net_init evaluates it with the network's
+// action_dim);  the bag passes are the same kernels with the same requests.
+#define DTQN_MAX_OBS_TOKENS 128        /* obs_dim of a discrete observation */
+#define DTQN_MAX_EMBED_COLS 1024       /* obs_dim * embed_per_obs: input columns of the embedding linear */
+#define DTQN_MAX_TABLE_FLOATS 65536    /* vocab * embed_per_obs: floats of the embedding table */
+
+// Embedding gradient of the row-block path (dtqn_tiled.hip).  The resident kernel (tl_embed_bwd_kernel) keeps d(e_in) of a 64-row block as
+// ONE set of matrix-core items (at most 128 gathered columns) and private scatter tables of (row groups) x obs_dim x vocab x e floats in
+// LDS; an observation beyond either runs the panel kernel (tl_embed_bwd_panel_kernel), whose LDS does not grow with obs_dim * vocab.
+// (constexpr: the kernels lay their LDS out with the same two helpers)
+// row groups of a 64-row block walked by different threads of the resident scatter: 4 if the 512 threads allow, else 2 or 1
+static constexpr inline int dtqn_embed_bwd_row_groups(int ke) { return ke * 4 <= 512 ? 4 : ke * 2 <= 512 ? 2 : 1; }
+// leading dimension of the W_e chunk / d(e_in) tile of ke columns: >= ke rounded up to 16, == 16 mod 64
+static constexpr inline int dtqn_embed_bwd_ldk(int ke) { return ((((ke + 15) & ~15) - 16 + 63) / 64) * 64 + 16; }
+#define DTQN_EMBED_BWD_PANEL 128       /* gathered columns per panel of the panel kernel */
+static inline size_t dtqn_embed_bwd_lds(int discrete, int action_dim, int obs_dim, int vocab, int e) {
+    const int ke = obs_dim * e, ldk = dtqn_embed_bwd_ldk(ke);
+    size_t f = (size_t)64 * (action_dim + 1) + 64 + 4;                                     // action columns of dx0, actions
+    if (discrete)                                                                          // dx0 chunk | W_e chunk | d(e_in) | tokens | tables
+        f += (size_t)64 * 68 + (size_t)64 * ldk + (size_t)64 * ldk + (size_t)64 * obs_dim +
+             (size_t)dtqn_embed_bwd_row_groups(ke) * obs_dim * vocab * e;
+    return f * sizeof(float);
+}
+static inline int dtqn_embed_bwd_resident(int discrete, int action_dim, int obs_dim, int vocab, int e) {
+    if (!discrete) return 1;                                                               // action embedding only: a few KB
+    return (long long)obs_dim * e <= 128 && dtqn_embed_bwd_lds(discrete, action_dim, obs_dim, vocab, e) <= 150 * 1024;
+}
+static inline size_t dtqn_embed_bwd_panel_lds(int action_dim, int obs_dim) {
+    const int ldk = dtqn_embed_bwd_ldk(DTQN_EMBED_BWD_PANEL);
+    // action columns, actions | dx0 chunk | W_e chunk | d(e_in) of the panel | tokens | first-occurrence rows (one byte each)
+    return ((size_t)64 * (action_dim + 1) + 64 + 4 + (size_t)64 * 68 + (size_t)2 * 64 * ldk + (size_t)64 * obs_dim) * sizeof(float) +
+           (((size_t)64 * obs_dim + 3) & ~(size_t)3);
+}
+
 // The whole-sequence kernels exist as explicit instantiations <d_model, 16-row tiles, head_dim, waves> (dtqn_forward.hip:
 // dispatch_fwd, dtqn_backward.hip: td_backward): X(d, mt, hd, nw).  TRAIN = forward and backward exist; the first entry of a
 // (d, mt, hd) is the default wave count, the others are reached with DTQN_WAVES (A/B switch).  dtqn_net_init places a network on

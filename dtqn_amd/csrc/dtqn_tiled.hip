@@ -2753,20 +2753,14 @@ struct TlEmbedBwdArgs {
 // group) adds its rows into a private [token][c] column of an LDS table (no two threads share an address), and the
 // O * (row groups) private tables are summed in a fixed order at the end -- deterministic, no atomics.  The tokens and
 // actions of the block are staged in LDS once (no global load inside the scatter loops).
-// row groups of a 64-row block walked by different threads of the scatter: 4 if the thread count allows, else 2 or 1
-static __host__ __device__ inline int emb_row_groups(int ke) { return ke * 4 <= TNT ? 4 : ke * 2 <= TNT ? 2 : 1; }
+// row groups of a 64-row block walked by different threads of the scatter, leading dimension of the W_e chunk / d(e_in), and the byte
+// count below: dtqn_limits.h, next to the predicate that says which observations this kernel serves (dtqn_embed_bwd_resident)
+static __host__ __device__ inline int emb_row_groups(int ke) { return dtqn_embed_bwd_row_groups(ke); }
 constexpr int kEbKC = 64, kEbLDT = kEbKC + 4;
-static __host__ __device__ inline int emb_bwd_ldk(int ke) {            // leading dim of the W_e chunk / d(e_in): >= KE16, == 16 mod 64
-    const int ke16 = (ke + 15) & ~15;
-    return ((ke16 - 16 + 63) / 64) * 64 + 16;
-}
+static __host__ __device__ inline int emb_bwd_ldk(int ke) { return dtqn_embed_bwd_ldk(ke); }
+static_assert(TROWS == 64 && TNT == 512 && kEbLDT == 68, "dtqn_limits.h spells these out in its embedding-gradient byte counts");
 static inline size_t tl_embed_bwd_lds(const DtqnNet& net) {
-    const int ldk = emb_bwd_ldk(net.ke);
-    size_t f = (size_t)TROWS * (net.action_dim + 1) + TROWS + 4;                           // action columns of dx0, actions
-    if (net.discrete)
-        f += (size_t)TROWS * kEbLDT + (size_t)kEbKC * ldk + (size_t)TROWS * ldk + (size_t)TROWS * net.obs_dim +
-             (size_t)emb_row_groups(net.ke) * net.obs_dim * net.vocab * net.embed_per_obs;
-    return f * sizeof(float);
+    return dtqn_embed_bwd_lds(net.discrete, net.action_dim, net.obs_dim, net.vocab, net.embed_per_obs);
 }
 __global__ __launch_bounds__(TNT) void tl_embed_bwd_kernel(TlEmbedBwdArgs a) {
     const DtqnNet& net = a.net;
@@ -2870,6 +2864,144 @@ __global__ __launch_bounds__(TNT) void tl_embed_bwd_kernel(TlEmbedBwdArgs a) {
         }
     } else {
         __syncthreads();
+    }
+    if (adim > 0) {
+        for (int idx = tid; idx < A * adim; idx += TNT) {
+            const int v = idx / adim, c = idx - v * adim;
+            float g = 0.f;
+            for (int rl = 0; rl < nrows; ++rl)
+                if (actl[rl] == v) g += Al[rl * (adim + 1) + c];
+            srec[net.so_act + idx] = a.bag ? srec[net.so_act + idx] + g : g;
+        }
+    }
+}
+
+// The same job for observations the resident kernel does not hold (dtqn_embed_bwd_resident false: more than 128 gathered columns, or
+// scatter tables beyond LDS): same grid, same arguments, same outputs, LDS independent of the vocabulary and linear in obs_dim only
+// through the staged tokens (dtqn_embed_bwd_panel_lds).
+//   * d(e_in) runs in column PANELS of at most 128 gathered columns -- the four accumulator items a wave keeps -- with the resident
+//     kernel's MFMA loop and leading dimensions; a panel ends on a token-slot boundary wherever one lies inside it (embed_per_obs need
+//     not divide 128; a slot wider than a panel is walked in pieces).
+//   * rep[r][j] = first row of the block whose token in slot j equals row r's.  Thread k of a panel walks the live rows in order and adds
+//     d(e_in)[r][k] onto d(e_in)[rep][k] IN PLACE: one thread per column, so no two threads share an address, and the row of the first
+//     occurrence ends up holding the sum over its token's rows in row order.
+//   * the V x e table partial of the record is zeroed first (context pass; the bag pass adds to what is there), then flushed slot by
+//     slot with a workgroup barrier between slots: the representatives of one slot hold distinct tokens, so every address has one
+//     writer at a time, and the barriers fix the order of the additions across slots and panels.
+// No atomics, a fixed summation order (the same update twice gives the same bits), tokens clamped and dead rows skipped as above.
+constexpr int kEbPanel = DTQN_EMBED_BWD_PANEL;
+__global__ __launch_bounds__(TNT) void tl_embed_bwd_panel_kernel(TlEmbedBwdArgs a) {
+    const DtqnNet& net = a.net;
+    const Thr t = make_thr();
+    const int tid = t.tid;
+    const int rpb = net.lp / TROWS, b = (int)blockIdx.x / rpb, rb = (int)blockIdx.x % rpb, row0 = rb * TROWS;
+    const int D = net.d_model, L = a.rows, A = net.num_actions, adim = net.action_dim;
+    if (a.bag && row0 >= L) return;                                    // bag pass: nothing of the bag in this row block
+    const float* DX = a.grd + (size_t)b * net.grd_stride + (a.bag ? a.dx_off : net.go_dx0) + (size_t)row0 * D;
+    float* srec = a.small + ((size_t)b * rpb + rb) * net.sp_stride;
+    const bool direct = a.bag || a.ep_idx == nullptr;
+    const int ep = direct ? b : a.ep_idx[b], st0 = direct ? 0 : a.start[b];
+    const float* obs_rows = a.obs + (size_t)ep * a.obs_ep_stride + (size_t)(st0 + row0) * net.obs_dim;
+    const uint8_t* act_rows = a.actions + (size_t)ep * a.act_ep_stride + st0;
+    int nrows = L - row0 < TROWS ? L - row0 : TROWS;                   // live rows of this block
+    nrows = nrows < 0 ? 0 : nrows;
+    const int KE = net.ke, e = net.embed_per_obs, V = net.vocab, O = net.obs_dim, DO = D - adim;
+    constexpr int LDK = dtqn_embed_bwd_ldk(kEbPanel);
+    float* Al = reinterpret_cast<float*>(dtqn_smem);                   // [64][adim + 1]  action columns of dx0
+    int* actl = reinterpret_cast<int*>(Al + TROWS * (adim + 1));       // [64 + 4] the action that pairs with row r (tl_embed_bwd_kernel)
+    float* Tl = reinterpret_cast<float*>(actl + TROWS + 4);            // [64][kEbLDT]  chunk of dx0[:, a:]
+    float* Wl = Tl + TROWS * kEbLDT;                                   // [64][LDK]     chunk of W_e, the panel's columns
+    float* dein = Wl + (size_t)kEbKC * LDK;                            // [64][LDK]     dL/d(gathered table rows) of the panel
+    int* tokl = reinterpret_cast<int*>(dein + (size_t)TROWS * LDK);    // [64][O] clamped tokens
+    uint8_t* repl = reinterpret_cast<uint8_t*>(tokl + TROWS * O);      // [64][O] first row of the block with the same token in the slot
+    if (adim > 0) {
+        for (int idx = tid; idx < TROWS * adim; idx += TNT) {
+            const int rl = idx / adim, c = idx - rl * adim;
+            Al[rl * (adim + 1) + c] = rl < nrows ? DX[(size_t)rl * D + c] : 0.f;
+        }
+        for (int rl = tid; rl < TROWS; rl += TNT) {
+            const int r = row0 + rl;
+            int v = -1;
+            if (rl < nrows) {
+                if (a.bag) v = (int)act_rows[r];
+                else if (L == 1) v = (int)act_rows[0];
+                else if (r > 0) v = (int)act_rows[r - 1];
+            }
+            actl[rl] = v;
+        }
+    }
+    for (int idx = tid; idx < TROWS * O; idx += TNT) {
+        const int rl = idx / O;
+        int tok = rl < nrows ? (int)obs_rows[idx] : 0;
+        tokl[idx] = tok < 0 ? 0 : (tok >= V ? V - 1 : tok);
+    }
+    if (!a.bag)
+        for (int idx = tid; idx < V * e; idx += TNT) srec[net.so_tab + idx] = 0.f;
+    __syncthreads();
+    for (int idx = tid; idx < TROWS * O; idx += TNT) {
+        const int rl = idx / O, j = idx - rl * O, tok = tokl[idx];
+        int rp = 0;
+        while (rp < rl && tokl[rp * O + j] != tok) ++rp;
+        repl[idx] = (uint8_t)rp;
+    }
+    const float* __restrict__ We = a.theta + net.off_obs_w;
+    for (int p0 = 0; p0 < KE;) {
+        int p1 = KE - p0 < kEbPanel ? KE : p0 + kEbPanel;
+        if (p1 < KE && (p1 / e) * e > p0) p1 = (p1 / e) * e;           // end on a slot boundary where one lies inside the panel
+        const int pc = p1 - p0, NT16 = (pc + 15) / 16, items = 4 * NT16;
+        f32x4 acc[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc[q] = zero4();
+        for (int k0 = 0; k0 < DO; k0 += kEbKC) {
+            const int kc = DO - k0 < kEbKC ? DO - k0 : kEbKC, kc4 = (kc + 3) & ~3;
+            __syncthreads();                                           // previous chunk consumed (and the previous panel flushed)
+            for (int idx = tid; idx < TROWS * kc4; idx += TNT) {
+                const int rl = idx / kc4, kl = idx - rl * kc4;
+                Tl[rl * kEbLDT + kl] = (rl < nrows && kl < kc) ? DX[(size_t)rl * D + adim + k0 + kl] : 0.f;
+            }
+            for (int idx = tid; idx < kc4 * NT16 * 16; idx += TNT) {
+                const int kl = idx / (NT16 * 16), k = idx - kl * (NT16 * 16);
+                Wl[kl * LDK + k] = (kl < kc && k < pc) ? We[(size_t)(k0 + kl) * KE + p0 + k] : 0.f;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int item = t.wave + q * TNW;
+                if (item < items) {
+                    const int nt = item >> 2, mt = item & 3;
+                    const float* ap = Tl + (mt * 16 + t.i) * kEbLDT + t.kq;
+                    const float* bp = Wl + t.kq * LDK + nt * 16 + t.i;
+                    for (int k = 0; k < kc4; k += 4) acc[q] = mfma16(ap[k], bp[(size_t)k * LDK], acc[q]);
+                }
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int item = t.wave + q * TNW;
+            if (item < items) {
+                const int nt = item >> 2, mt = item & 3;
+#pragma unroll
+                for (int r4 = 0; r4 < 4; ++r4) dein[(mt * 16 + t.kq * 4 + r4) * LDK + nt * 16 + t.i] = acc[q][r4];
+            }
+        }
+        __syncthreads();
+        if (tid < pc) {
+            const int j = (p0 + tid) / e;
+            for (int rl = 1; rl < nrows; ++rl) {
+                const int rp = (int)repl[rl * O + j];
+                if (rp != rl) dein[rp * LDK + tid] += dein[rl * LDK + tid];
+            }
+        }
+        const int j0 = p0 / e, j1 = (p1 - 1) / e;
+        for (int j = j0; j <= j1; ++j) {
+            __syncthreads();                                           // the sums stand; the previous slot's additions are done
+            const int c0 = p0 > j * e ? p0 - j * e : 0, c1 = p1 < (j + 1) * e ? p1 - j * e : e, nc = c1 - c0;
+            for (int idx = tid; idx < nrows * nc; idx += TNT) {
+                const int rl = idx / nc, c = c0 + idx - rl * nc;
+                if ((int)repl[rl * O + j] == rl) srec[net.so_tab + tokl[rl * O + j] * e + c] += dein[rl * LDK + j * e + c - p0];
+            }
+        }
+        p0 = p1;
     }
     if (adim > 0) {
         for (int idx = tid; idx < A * adim; idx += TNT) {
@@ -4326,16 +4458,22 @@ static int backward_records(const DtqnNet& net, const BwdIn& in, const DtqnTd& t
         a.net = net; a.theta = theta; a.grd = grd; a.small = td.small;
         a.obs = in.src.obs; a.actions = in.src.actions; a.obs_ep_stride = in.src.obs_ep_stride; a.act_ep_stride = in.src.act_ep_stride;
         a.ep_idx = in.src.ep_idx; a.start = in.src.start;
-        const size_t lds = tl_embed_bwd_lds(net);
-        // (KE <= 256: at most 4 x 16 column tiles x 4 row tiles = the 4 items a wave keeps accumulators for)
-        if (lds > 150 * 1024 || (net.discrete && net.ke > 128)) return DTQN_ERR_CONFIG;
+        // the resident kernel while its d(e_in) items and scatter tables fit (every network of BASELINE), the panel kernel beyond:
+        // decided by the observation's shape alone, which dtqn_net_init has bounded -- one of the two always runs
+        const bool resident = dtqn_embed_bwd_resident(net.discrete, net.action_dim, net.obs_dim, net.vocab, net.embed_per_obs) != 0;
+        const size_t lds = resident ? tl_embed_bwd_lds(net) : dtqn_embed_bwd_panel_lds(net.action_dim, net.obs_dim);
+        auto launch = [&]() -> int {
+            if (resident) TL_LAUNCH(tl_embed_bwd_kernel, dim3(B * rpb), dim3(TNT), lds, stream, a);
+            else TL_LAUNCH(tl_embed_bwd_panel_kernel, dim3(B * rpb), dim3(TNT), lds, stream, a);
+            return DTQN_OK;
+        };
         a.bag = 0; a.dx_off = 0; a.rows = L;
-        TL_LAUNCH(tl_embed_bwd_kernel, dim3(B * rpb), dim3(TNT), lds, stream, a);
+        if ((rc = launch()) != DTQN_OK) return rc;
         if (net.bag_size > 0) {          // the bag entries went through the same tables: their partials are added
             a.obs = in.src.bag_obs; a.actions = in.src.bag_actions; a.ep_idx = nullptr; a.start = nullptr;
             a.obs_ep_stride = (long long)net.bag_size * net.obs_dim; a.act_ep_stride = net.bag_size;
             a.bag = 1; a.dx_off = net.go_bag_de; a.rows = net.bag_size;
-            TL_LAUNCH(tl_embed_bwd_kernel, dim3(B * rpb), dim3(TNT), lds, stream, a);
+            if ((rc = launch()) != DTQN_OK) return rc;
         }
     }
     return DTQN_OK;

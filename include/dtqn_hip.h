@@ -50,7 +50,8 @@ typedef struct DtqnNet {
     /* ---- inputs (dtqn.py:41-59 ctor arguments) ---- */
     int32_t obs_dim;          /* O: length of the observation vector */
     int32_t num_actions;      /* A */
-    int32_t embed_per_obs;    /* e: per-dimension embedding width (discrete obs only) */
+    int32_t embed_per_obs;    /* e: per-dimension embedding width (discrete obs only).  Admitted: obs_dim <= 128, obs_dim * e <= 1024, vocab * e <= 65536
+                               * (dtqn_limits.h; d_model 16 / 32: obs_dim * e <= 3 * d_model) -- every such observation trains on every admitted network */
     int32_t action_dim;       /* a: action-embedding width, 0 = none */
     int32_t d_model;          /* D: inner_embed_size */
     int32_t num_heads;        /* H */
