@@ -100,6 +100,27 @@ inline int device_cu_count() {
 #else
 #define DTQN_PROF(buf, slot) ((void)(slot))
 #endif
+// The same clock read into a (scalar) register now and stored at the end of the kernel with DTQN_PROF_PUT: nothing is stored between
+// a kernel's loads and their use, so the mark behind "all loads issued" does not turn into the loads' round trip (docs/HISTORY.md 6e).
+// DTQN_PROF_SETTLE(x...): the values named have arrived in registers before the clock is read ("tile and job known").
+#ifdef DTQN_ENABLE_PROF
+#define DTQN_PROF_CLOCK(var) do { DTQN_SCHED_FENCE(); (var) = (long long)wall_clock64(); DTQN_SCHED_FENCE(); } while (0)
+#define DTQN_PROF_SETTLE(x0, x1, x2, x3) asm volatile("" : : "s"(x0), "s"(x1), "s"(x2), "s"(x3))
+#define DTQN_PROF_PUT(buf, slot, var) \
+    do { if ((buf) != nullptr && (blockIdx.x == 0 || blockIdx.x == DTQN_PROF_WG1) && threadIdx.x == 0) (buf)[(blockIdx.x == 0 ? 0 : 32) + (slot)] = (var); } while (0)
+#else
+#define DTQN_PROF_CLOCK(var) ((void)(var))
+#define DTQN_PROF_SETTLE(x0, x1, x2, x3) ((void)0)
+#define DTQN_PROF_PUT(buf, slot, var) ((void)(var))
+#endif
+
+// DTQN_SGPR_PIN(x...): the (wave-uniform) values named are in scalar registers at this point.  At the top of a kernel it gathers the
+// kernel-argument loads of everything named into one batch in front of the first branch, instead of one dependent round trip per branch.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define DTQN_SGPR_PIN4(x0, x1, x2, x3) asm volatile("" : : "s"(x0), "s"(x1), "s"(x2), "s"(x3))
+#else
+#define DTQN_SGPR_PIN4(x0, x1, x2, x3) ((void)0)
+#endif
 
 #include <dtqn_gfx950.hpp>
 

@@ -11,6 +11,8 @@
 // of one dY row and its B operands 4 consecutive floats of one X row: every global access is a
 // coalesced 16 B/lane load, 16 MFMAs per pair of loads.  The four waves take different sequences
 // and are summed through LDS; splits are summed by dtqn_td_reduce (deterministic, no atomics).
+#include <climits>
+#include <cstring>
 #include <mutex>
 #include "dtqn_device.hpp"
 #include "dtqn_wgrad_direct.hpp"
@@ -386,7 +388,7 @@ static inline bool wgrad_lds_enabled(const DtqnNet& net) {
 struct WgradDirectArgs {
     DtqnNet net;
     DtqnWJob jobs[kMaxWJobs];
-    int dtile0[kMaxWJobs];  // first direct tile of each job
+    int dtile0[kMaxWJobs];  // first direct tile of each job; INT_MAX behind the last job
     const float* act;
     const float* grd;
     float* grad;            // [n_trainable]
@@ -395,12 +397,17 @@ struct WgradDirectArgs {
     int32_t* step_counter;
     int batch, n_jobs, n_small, row_split;
     int n_tiles, n_parts;
-    int slots;              // tile workgroups per XCD: workgroup b (on XCD b % 8) takes tile xcd_tile0[b % 8] + b / 8
-    int xcd_tile0[8], xcd_ntiles[8];
+    int slots;              // tile workgroups per XCD: workgroup b (on XCD b % 8) takes tile (b % 8) * slots + b / 8
     int xcd_map;            // 0: tile = workgroup index (A/B timing)
     int small_per;          // per-sequence-partial elements per workgroup: kDSmall, or 2 kDSmall where that brings the grid down to one round
+    long long* prof;        // stage clocks of workgroups 0 and DTQN_PROF_WG1 (DTQN_ENABLE_PROF builds; slots 16 .. 21 of the forward's half)
 };
+static_assert(sizeof(WgradDirectArgs) <= 4096, "kernel arguments of one launch");
 
+// A tile workgroup reaches its work in two scalar round trips: everything that does not depend on the job -- the launch's scalars, the
+// pointers, the tile starts of the jobs -- is fetched in one batch in front of the first branch, the tile follows from the workgroup
+// index by arithmetic, the job from compares on the tile starts, and the job's own fields are the one dependent fetch.  (Fetched where
+// each branch first asked, they were six trips one behind the other: 1.6 us from kernel entry to a known job on the stage clock.)
 __global__ __launch_bounds__(kDirectThreads) void dtqn_wgrad_direct_kernel(WgradDirectArgs a) {
     const Thr t = make_thr();
     const DtqnNet& net = a.net;
@@ -408,23 +415,51 @@ __global__ __launch_bounds__(kDirectThreads) void dtqn_wgrad_direct_kernel(Wgrad
     float* red = reinterpret_cast<float*>(dtqn_smem);                     // [waves] block reduction of the sum of squares
     float* slabs = red + kDirectWaves;
     float ss = 0.f;                                                       // this thread's share of sum(g^2)
-    const int b = (int)blockIdx.x, tile_blocks = a.slots * 8;
+    long long clk_entry = 0, clk_job = 0, clk_norm = 0;
+    DirectClk clk;
+    DTQN_PROF_CLOCK(clk_entry);
+    const int b = (int)blockIdx.x, slots = a.slots, n_tiles = a.n_tiles, n_parts = a.n_parts, xcd_map = a.xcd_map, n_jobs = a.n_jobs;
+    const DirectCtx ctx{a.act, a.grd, a.small, a.grad, a.batch, a.row_split, a.n_small};
+    float* const norm_partial = a.norm_partial;
+    int d0[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) d0[k] = a.dtile0[k];
+    DTQN_SGPR_PIN4(slots, n_tiles, n_parts, xcd_map);
+    DTQN_SGPR_PIN4(n_jobs, ctx.batch, ctx.act, ctx.grd);
+    DTQN_SGPR_PIN4(ctx.grad, norm_partial, net.act_stride, net.grd_stride);
+    DTQN_SGPR_PIN4(d0[0], d0[1], d0[2], d0[3]); DTQN_SGPR_PIN4(d0[4], d0[5], d0[6], d0[7]);
+    DTQN_SGPR_PIN4(d0[8], d0[9], d0[10], d0[11]); DTQN_SGPR_PIN4(d0[12], d0[13], d0[14], d0[15]);
+    const int tile_blocks = slots * 8;
     if (b == 0 && tid == 0) a.step_counter[0] = a.step_counter[1];        // publish the step count of the previous update
     if (b == 0)                                                           // partials nobody writes this time
-        for (int i = (int)gridDim.x + tid; i < a.n_parts; i += kDirectThreads) a.norm_partial[i] = 0.f;
-    const int tile = b >= tile_blocks ? a.n_tiles : !a.xcd_map ? b : b / 8 < a.xcd_ntiles[b % 8] ? a.xcd_tile0[b % 8] + b / 8 : a.n_tiles;
-    const DirectCtx ctx{a.act, a.grd, a.small, a.grad, a.batch, a.row_split, a.n_small};
+        for (int i = (int)gridDim.x + tid; i < n_parts; i += kDirectThreads) norm_partial[i] = 0.f;
+    // eight equal runs of consecutive tiles, one per XCD (direct_plan): run b % 8 starts at tile (b % 8) * slots
+    const int run_tile = (b & 7) * slots + (b >> 3);
+    const int tile = b >= tile_blocks ? n_tiles : !xcd_map ? b : run_tile < n_tiles ? run_tile : n_tiles;
     if (b >= tile_blocks) {
         // (same sums in the same order whatever the block size: an element's records are added wave by wave, then the waves in order)
         ss = a.small_per == 2 * kDSmall ? direct_small<false, 2 * kDSmall, kDirectWaves>(net, ctx, b - tile_blocks, slabs, t)
                                         : direct_small<false, kDSmall, kDirectWaves>(net, ctx, b - tile_blocks, slabs, t);
-    } else if (tile < a.n_tiles) {
-        int j = 0;
-        for (int k = 1; k < a.n_jobs; ++k)
-            if (a.dtile0[k] <= tile) j = k;
-        ss = direct_tile<false, kDirectWaves>(net, ctx, a.jobs[j], tile - a.dtile0[j], slabs, t);
+    } else if (tile < n_tiles) {
+        int j = 0;                                                        // tile starts ascend: the job is the number of starts at or below the tile
+#pragma unroll
+        for (int k = 1; k < 16; ++k) j += d0[k] <= tile ? 1 : 0;
+        if (n_jobs > 16)
+            for (int k = 16; k < n_jobs; ++k) j += a.dtile0[k] <= tile ? 1 : 0;
+        const DtqnWJob job = a.jobs[j];                                   // the one dependent fetch: every field of the job in one batch
+        const int local = tile - a.dtile0[j];
+        DTQN_SGPR_PIN4(job.x_in_act, job.x_off, job.ldx, job.K);
+        DTQN_SGPR_PIN4(job.dy_off, job.ldy, job.N, job.w_off);
+        DTQN_SGPR_PIN4(job.b_off, job.n_layers, job.x_lstride, job.dy_lstride);
+        DTQN_SGPR_PIN4(local, net.lp, job.ldy, job.ldx);
+        DTQN_PROF_CLOCK(clk_job);
+        ss = direct_tile<false, kDirectWaves>(net, ctx, job, local, slabs, t, clk);
     }
-    direct_norm_partial<kDirectWaves>(ss, red, a.norm_partial, b, t);
+    direct_norm_partial<kDirectWaves>(ss, red, norm_partial, b, t);
+    DTQN_PROF_CLOCK(clk_norm);
+    // marks 16 .. 21: entry | tile and job known | all loads issued | last MFMA done | slabs reduced, grad stored | norm partial stored
+    DTQN_PROF_PUT(a.prof, 16, clk_entry); DTQN_PROF_PUT(a.prof, 17, clk_job); DTQN_PROF_PUT(a.prof, 18, clk.loads);
+    DTQN_PROF_PUT(a.prof, 19, clk.mfma); DTQN_PROF_PUT(a.prof, 20, clk.stored); DTQN_PROF_PUT(a.prof, 21, clk_norm);
 }
 
 // direct tiles of a net: per job ceil(N / 16) * ceil(K / 32)
@@ -441,20 +476,15 @@ struct DirectPlan {
     int n_tiles, slots, grid;
     int small_per;          // elements of the per-sequence partials per workgroup
     int grid_max;           // the grid with the smaller blocks (what norm_partial is sized for)
-    int xcd_tile0[8], xcd_ntiles[8];
 };
-// Which tiles each XCD takes: eight equal runs of consecutive tiles.  (Measured at cfg 1, batch 32: tile = workgroup
+// Which tiles each XCD takes: eight equal runs of consecutive tiles, `slots` each (the kernel derives a run's start from the workgroup
+// index).  (Measured at cfg 1, batch 32: tile = workgroup
 // index, i.e. every XCD sees every matrix, 116.7 us / update; equal runs 113.3; whole matrices per XCD, which leaves
 // XCDs with 8 - 32 tiles, 116.4.)  DTQN_WGRAD_XCD=0 gives the first for A/B timing.
 static DirectPlan direct_plan(const DtqnNet* net, const DtqnWJob* jobs) {
     DirectPlan p;
     p.n_tiles = direct_tiles(net, jobs, p.dtile0);
-    const int per = (p.n_tiles + 7) / 8;
-    for (int x = 0; x < 8; ++x) {
-        p.xcd_tile0[x] = x * per < p.n_tiles ? x * per : p.n_tiles;
-        p.xcd_ntiles[x] = p.n_tiles - p.xcd_tile0[x] < per ? p.n_tiles - p.xcd_tile0[x] : per;
-    }
-    p.slots = per;
+    p.slots = (p.n_tiles + 7) / 8;
     // The blocks that sum the per-sequence partials are short; with kDSmall elements each, BASELINE config 1 is 240 + 29 = 269
     // workgroups on 256 compute units -- 13 of them wait for a second round.  Twice the elements per block (255 workgroups) is one
     // round; taken only when it makes that difference.  DTQN_DSMALL=<kDSmall | 2 kDSmall> overrides (A/B timing).
@@ -522,24 +552,60 @@ extern "C" int dtqn_td_norm_partials(const DtqnNet* net) {
     return opt > dir ? opt : dir;
 }
 
-static int wgrad_direct(const DtqnNet* net, const DtqnTd* td, hipStream_t stream) {
-    WgradDirectArgs a;
+// Everything of a launch that follows from (network, batch, compute units of the device): the job list, the tile plan, the switches
+// read from the environment.  Built once and kept -- an update only fills in the buffers of its DtqnTd.  Entries are found by VALUE
+// (the whole DtqnNet, the batch, the CU count), so a caller may rebuild or move its structs freely; the switches (DTQN_WGRAD_XCD,
+// DTQN_DSMALL) are read when an entry is built, that is once per (network, batch) of a process.
+struct DirectLaunch {
+    DtqnNet net;
+    int batch, cus, grid, rc;
+    WgradDirectArgs args;
+};
+static int direct_launch_build(const DtqnNet* net, int batch, int cus, DirectLaunch* l) {
+    std::memset(l, 0, sizeof(*l));
+    l->net = *net; l->batch = batch; l->cus = cus;
+    WgradDirectArgs& a = l->args;
     a.net = *net;
     if (dtqn_net_wjobs(net, a.jobs) != DTQN_OK) return DTQN_ERR_CONFIG;
     for (int j = 0; j < net->n_wjobs; ++j)      // a wave's units must fit the register buffers direct_tile was compiled with
-        if ((long long)td->batch * net->lp * a.jobs[j].n_layers > kDirectMaxTokens) return DTQN_ERR_CONFIG;
+        if ((long long)batch * net->lp * a.jobs[j].n_layers > kDirectMaxTokens) return DTQN_ERR_CONFIG;
     const DirectPlan plan = direct_plan(net, a.jobs);
     a.n_tiles = plan.n_tiles; a.slots = plan.slots; a.small_per = plan.small_per;
-    for (int j = 0; j < net->n_wjobs; ++j) a.dtile0[j] = plan.dtile0[j];
-    for (int x = 0; x < 8; ++x) { a.xcd_tile0[x] = plan.xcd_tile0[x]; a.xcd_ntiles[x] = plan.xcd_ntiles[x]; }
-    a.act = td->act; a.grd = td->grd; a.grad = td->grad; a.small = td->small;
-    a.norm_partial = td->norm_partial; a.step_counter = td->step_counter;
-    a.batch = td->batch; a.n_jobs = net->n_wjobs; a.n_small = small_elems(net);
-    a.row_split = td->row_split > 1 ? td->row_split : 1;
+    for (int j = 0; j < kMaxWJobs; ++j) a.dtile0[j] = j < net->n_wjobs ? plan.dtile0[j] : INT_MAX;
+    a.batch = batch; a.n_jobs = net->n_wjobs; a.n_small = small_elems(net);
     a.n_parts = dtqn_td_norm_partials(net);
     const char* xm = getenv("DTQN_WGRAD_XCD");
     a.xcd_map = xm != nullptr ? atoi(xm) : 1;
-    const int grid = plan.grid;
+    l->grid = plan.grid;
+    return DTQN_OK;
+}
+static int wgrad_direct(const DtqnNet* net, const DtqnTd* td, hipStream_t stream) {
+    constexpr int kEntries = 8;
+    static DirectLaunch cache[kEntries];
+    static int used = 0, next = 0;
+    static std::mutex mu;
+    WgradDirectArgs a;
+    int grid = 0;
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        const int cus = fuse_cu_count();
+        const DirectLaunch* hit = nullptr;
+        for (int i = 0; i < used && hit == nullptr; ++i)
+            if (cache[i].batch == td->batch && cache[i].cus == cus && std::memcmp(&cache[i].net, net, sizeof(DtqnNet)) == 0) hit = &cache[i];
+        if (hit == nullptr) {
+            DirectLaunch* l = &cache[used < kEntries ? used : next];
+            l->rc = direct_launch_build(net, td->batch, cus, l);
+            if (used < kEntries) ++used; else next = (next + 1) % kEntries;
+            hit = l;
+        }
+        if (hit->rc != DTQN_OK) return hit->rc;
+        a = hit->args;
+        grid = hit->grid;
+    }
+    a.act = td->act; a.grd = td->grd; a.grad = td->grad; a.small = td->small;
+    a.norm_partial = td->norm_partial; a.step_counter = td->step_counter;
+    a.row_split = td->row_split > 1 ? td->row_split : 1;
+    a.prof = static_cast<long long*>(dtqn_debug_profile_buffer());
     const size_t lds = kDirectLdsFloats * sizeof(float);
     (void)hipGetLastError();   // drop stale errors left by other users of the runtime
     hipLaunchKernelGGL(dtqn_wgrad_direct_kernel, dim3(grid), dim3(kDirectThreads), lds, stream, a);

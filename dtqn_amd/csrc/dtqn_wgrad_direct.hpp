@@ -37,6 +37,10 @@ struct DirectCtx {
     float* grad;
     int batch, row_split, n_small;
 };
+// stage clocks of one tile workgroup (DTQN_ENABLE_PROF builds; dtqn_wgrad_direct_kernel stores them behind its last barrier)
+struct DirectClk {
+    long long loads = 0, mfma = 0, stored = 0;
+};
 
 // SC1: the grd / small records were written by OTHER workgroups of the same launch with write-through (sc1) stores; they are read
 // with sc1 loads (L1 bypassed; this XCD's L2 holds no older copy: nothing of this launch read them before their flag went up)
@@ -49,7 +53,8 @@ __device__ __forceinline__ float direct_ld(const float* base, const DtqnRsrc& rs
 // One 16 x 32 tile of one dW (+ its slice of db): contracts every token of the batch, writes `grad`, returns this thread's share
 // of the tile's sum of squares.  `slabs`: kDirectWaves * (kDTN + 1) * (kDTK + 4) floats of LDS.  Contains one __syncthreads().
 template <bool SC1, int WV>
-__device__ __forceinline__ float direct_tile(const DtqnNet& net, const DirectCtx& a, const DtqnWJob& job, int local, float* slabs, const Thr& t) {
+__device__ __forceinline__ float direct_tile(const DtqnNet& net, const DirectCtx& a, const DtqnWJob& job, int local, float* slabs, const Thr& t,
+                                             DirectClk& clk) {
     const int LP = net.lp, tid = t.tid;
     float ss = 0.f;
     const int tiles_k = (job.K + kDTK - 1) / kDTK;
@@ -121,6 +126,7 @@ __device__ __forceinline__ float direct_tile(const DtqnNet& net, const DirectCtx
     if constexpr (kMaxGroups == 1) {
         group_load(av[0], bv[0]);
         DTQN_SCHED_FENCE();
+        DTQN_PROF_CLOCK(clk.loads);
         group_mma(0, av[0], bv[0]);
     } else {
         constexpr int B1 = NBUF - 1;
@@ -147,6 +153,10 @@ __device__ __forceinline__ float direct_tile(const DtqnNet& net, const DirectCtx
             group_mma(g, av[0], bv[0]);
         }
     }
+#ifdef DTQN_ENABLE_PROF
+    asm volatile("" : "+v"(acc[0]), "+v"(acc[1]));                      // the last MFMA has delivered
+#endif
+    DTQN_PROF_CLOCK(clk.mfma);
     // bias: sum over the 4 token phases of this lane's dY column
     bsum += __shfl_xor(bsum, 16);
     bsum += __shfl_xor(bsum, 32);
@@ -188,6 +198,7 @@ __device__ __forceinline__ float direct_tile(const DtqnNet& net, const DirectCtx
             ss = v * v;
         }
     }
+    DTQN_PROF_CLOCK(clk.stored);
     return ss;
 }
 
@@ -332,7 +343,8 @@ __device__ __forceinline__ void fuse_role(const DtqnNet& net, const FuseArgs& f,
                 if (f.dtile0[k] <= p) j = k;
             const int ev = f.job_event[j];
             if (ev > waited) { fuse_wait(f.counters + ev, f.n_chain, t); waited = ev; }
-            ss += direct_tile<!DTQN_FUSE_DEBUG_PLAINLD, NW>(net, ctx, f.jobs[j], p - f.dtile0[j], slabs, t);
+            DirectClk clk;
+            ss += direct_tile<!DTQN_FUSE_DEBUG_PLAINLD, NW>(net, ctx, f.jobs[j], p - f.dtile0[j], slabs, t, clk);
         } else {
             if (net.num_layers > waited) { fuse_wait(f.counters + net.num_layers, f.n_chain, t); waited = net.num_layers; }
             ss += direct_small<!DTQN_FUSE_DEBUG_PLAINLD, kDSmallFused, NW>(net, ctx, p - f.n_tiles, slabs, t);
