@@ -108,10 +108,14 @@ inline int device_cu_count() {
 #define DTQN_PROF_SETTLE(x0, x1, x2, x3) asm volatile("" : : "s"(x0), "s"(x1), "s"(x2), "s"(x3))
 #define DTQN_PROF_PUT(buf, slot, var) \
     do { if ((buf) != nullptr && (blockIdx.x == 0 || blockIdx.x == DTQN_PROF_WG1) && threadIdx.x == 0) (buf)[(blockIdx.x == 0 ? 0 : 32) + (slot)] = (var); } while (0)
+// DTQN_PROF_PUT_HALF: the same store into the half the caller names (a kernel whose second profiled workgroup is not DTQN_PROF_WG1)
+#define DTQN_PROF_PUT_HALF(buf, half, slot, var) \
+    do { if ((buf) != nullptr && threadIdx.x == 0) (buf)[(half) * 32 + (slot)] = (var); } while (0)
 #else
 #define DTQN_PROF_CLOCK(var) ((void)(var))
 #define DTQN_PROF_SETTLE(x0, x1, x2, x3) ((void)0)
 #define DTQN_PROF_PUT(buf, slot, var) ((void)(var))
+#define DTQN_PROF_PUT_HALF(buf, half, slot, var) ((void)(var))
 #endif
 
 // DTQN_SGPR_PIN(x...): the (wave-uniform) values named are in scalar registers at this point.  At the top of a kernel it gathers the
