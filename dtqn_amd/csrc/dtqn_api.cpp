@@ -6,6 +6,7 @@
 #include "dtqn_actor.hpp"
 #include "dtqn_hip.h"
 #include "dtqn_limits.h"
+#include "dtqn_rollout.hpp"
 
 extern "C" const char* dtqn_build_info(void) {
 #ifdef DTQN_BUILD_INFO
@@ -253,6 +254,26 @@ extern "C" int dtqn_actor_greedy_batch(const DtqnNet* net, const float* theta, c
                                   stream)) != DTQN_OK)
         return rc;
     return dtqn::actor_greedy_rows(h.lens, q_dev, q_last_host, action_host, n_envs, n_max, net->num_actions, s);
+}
+
+// Device-resident rollout (dtqn_rollout.hip): the forward of dtqn_actor_forward_batch on the context block that lives in the rollout
+// state -- no host copy, the ragged lengths are read on the device -- then the one-workgroup step kernel.  Two launches, nothing between.
+extern "C" int dtqn_rollout_step(const DtqnNet* net, const float* theta, const DtqnReplay* rp, const DtqnRollout* ro, uint32_t vstep, int cur,
+                                 int n_max, float epsilon, int store, long long authorize, int run_forward, int train_mode, uint32_t dropout_seed,
+                                 uint32_t dropout_step, void* stream) {
+    int rc = dtqn::rollout_check(net, rp, ro);
+    if (rc != DTQN_OK) return rc;
+    if (cur != 0 && cur != 1) return DTQN_ERR_ARG;
+    if (run_forward) {
+        if (!theta || !ro->q_dev || (!net->tiled && !ro->q_last)) return DTQN_ERR_ARG;
+        if (n_max < 1 || n_max > net->ctx_len) return DTQN_ERR_ARG;                 // dtqn.py:170-173
+        const dtqn::RolloutLayout l = dtqn::rollout_layout(net, rp, ro);
+        const ActorBlock b = actor_block(net, static_cast<uint8_t*>(ro->state) + l.off[6 + cur], ro->n_envs);
+        rc = actor_batch_forward(net, theta, b, ro->n_envs, ro->n_envs, n_max, ro->q_dev, ro->q_last, ro->workspace, train_mode, dropout_seed,
+                                 dropout_step, stream);
+        if (rc != DTQN_OK) return rc;
+    }
+    return dtqn::rollout_step_launch(net, rp, ro, vstep, cur, n_max, epsilon, store, authorize, run_forward ? 1 : 0, (hipStream_t)stream);
 }
 
 // The differentiable forward without dropout (the function the no-grad forward computes): the _drop entry points with the masks off.

@@ -1,0 +1,45 @@
+// Device-resident rollout: the layout of its one state allocation and the launches dtqn_api.cpp sequences (dtqn_rollout.hip).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "dtqn_actor.hpp"
+#include "dtqn_hip.h"
+
+namespace dtqn {
+
+constexpr int kRolloutEnvInts = 40;        // Memory: current card | hidden values [cards] | shown table [cards], cards <= 16
+constexpr int kRolloutLastInts = 8;
+constexpr int kRolloutCounters = 8;
+
+// Byte offsets of the sections of DtqnRollout::state (include/dtqn_hip.h lists them), every section 16-byte aligned.
+struct RolloutLayout {
+    size_t off[DTQN_ROLLOUT_OFFSETS];
+    size_t bytes;
+    size_t block_bytes;
+};
+inline RolloutLayout rollout_layout(const DtqnNet* net, const DtqnReplay* rp, const DtqnRollout* ro) {
+    RolloutLayout l;
+    const int n_envs = ro->n_envs;
+    const size_t N = (size_t)n_envs, T = (size_t)rp->max_steps, O = (size_t)net->obs_dim, K = (size_t)ro->pending_slots;
+    l.block_bytes = (actor_block(net, nullptr, n_envs).bytes + 15) & ~(size_t)15;
+    const size_t sizes[DTQN_ROLLOUT_OFFSETS] = {8 * kRolloutCounters, 8 * N * 4,       4 * N * kRolloutEnvInts, 4 * N,     8 * N, 4 * N * kRolloutLastInts,
+                                                l.block_bytes,        l.block_bytes,   4 * N * (T + 1) * O,     N * T,     4 * N * T, N * T,
+                                                4 * K * (T + 1) * O,  K * T,           4 * K * T,               K * T,     4 * K};
+    size_t at = 0;
+    for (int k = 0; k < DTQN_ROLLOUT_OFFSETS; ++k) {
+        l.off[k] = at;
+        at += (sizes[k] + 15) & ~(size_t)15;
+    }
+    l.bytes = at;
+    return l;
+}
+
+// DTQN_OK when the descriptor, the network and the replay fit the kernels (flat f32 observations of the environment's width, ...)
+int rollout_check(const DtqnNet* net, const DtqnReplay* rp, const DtqnRollout* ro);
+int rollout_reset_launch(const DtqnNet* net, const DtqnReplay* rp, const DtqnRollout* ro, uint32_t vstep, hipStream_t stream);
+// q_rows: where the step kernel finds Q of the last live row -- q_last [N][A] (stride 0) or q_dev with n_max rows per sequence
+int rollout_step_launch(const DtqnNet* net, const DtqnReplay* rp, const DtqnRollout* ro, uint32_t vstep, int cur, int n_max, float epsilon,
+                        int store, long long authorize, int have_q, hipStream_t stream);
+int rollout_commit_launch(const DtqnNet* net, const DtqnReplay* rp, const DtqnRollout* ro, uint32_t vstep, long long authorize, hipStream_t stream);
+
+}  // namespace dtqn

@@ -387,6 +387,62 @@ int dtqn_actor_greedy_batch(const DtqnNet* net, const float* theta, const void* 
                             uint32_t dropout_seed, uint32_t dropout_step, void* stream);
 /* Tests: live sequences (the forward's batch) of the last dtqn_actor_greedy_batch / dtqn_img_actor_greedy_batch. */
 int dtqn_debug_last_actor_live(void);
+
+/* ------------------------------------------------------------------------------------------
+ * Device-resident rollout (dtqn_rollout.hip; DESIGN.md "Device-resident rollout"): N CarFlag or Memory environments, their rolling
+ * contexts, the episodes in progress and the episode accounting live in ONE device allocation (`state`); a vector step is the
+ * batched actor forward on the resident context block plus one one-workgroup kernel, with no host work in between.
+ * state layout (byte offsets from dtqn_rollout_state_bytes; T = rp->max_steps, O = obs_dim, L = ctx_len, A = num_actions):
+ *   [0] counters  i64[8]      episodes committed | env steps | successes | episodes finished | length sum | return sum (f64) |
+ *                             episodes staged (finished with store != 0) | episodes dropped (pending ring full: the host broke its bound)
+ *   [1] env_f64   f64[N][4]   CarFlag: position, velocity, direction, heaven position (+1 / -1)
+ *   [2] env_i32   i32[N][40]  Memory: current card | hidden values [cards] | shown table [cards]
+ *   [3] elapsed   i32[N]      steps of the episode in progress (= the context's timestep)
+ *   [4] ep_ret    f64[N]      its return so far
+ *   [5] last      i32[N][8]   last step: action | explored | done | stored done | truncated | success | episode reset | reward (f32 bits)
+ *   [6] block 0, [7] block 1  the packed actor block of dtqn_actor_forward_batch, twice (a step reads one and writes the other)
+ *   [8] stage_obs f32[N][T+1][O]   [9] stage_act u8[N][T]   [10] stage_rew f32[N][T]   [11] stage_done u8[N][T]   the episodes in progress
+ *   [12] pend_obs f32[K][T+1][O]   [13] pend_act u8[K][T]   [14] pend_rew f32[K][T]    [15] pend_done u8[K][T]    [16] pend_len i32[K]
+ *        the pending ring (K = pending_slots): episode k since attach waits in entry k mod K until a launch is authorised to write it
+ * ------------------------------------------------------------------------------------------ */
+#define DTQN_ROLLOUT_CARFLAG 0
+#define DTQN_ROLLOUT_MEMORY 1
+#define DTQN_ROLLOUT_OFFSETS 17
+#define DTQN_ROLLOUT_STATUS_WORDS 16
+typedef struct DtqnRollout {
+    void* state;                      /* device, dtqn_rollout_state_bytes() bytes, zeroed once by the caller */
+    void* status_host;                /* PINNED: DTQN_ROLLOUT_STATUS_WORDS granules {word, tag} of 8 bytes, zeroed once */
+    const int32_t* forced_actions;    /* device [N] or NULL: >= 0 overrides environment i's action (tests) */
+    float* q_last;                    /* device [N][A]: Q of the last live row (whole-sequence networks write it) */
+    float* q_dev;                     /* device [N][L][A] */
+    float* workspace;                 /* as dtqn_actor_forward_batch for N */
+    int32_t env_kind;                 /* DTQN_ROLLOUT_CARFLAG / DTQN_ROLLOUT_MEMORY */
+    int32_t n_envs;
+    int32_t max_episode_steps;        /* gym TimeLimit cap, <= rp->max_steps */
+    int32_t num_pairs;                /* Memory: pairs on the table (1..8) */
+    int32_t pos0;                     /* the k-th episode finished since attach goes to replay slot (pos0 + k) mod E */
+    int32_t pending_slots;            /* K: finished episodes that may wait for the host's go-ahead (>= those of the vector steps the host runs ahead) */
+    uint32_t seed;
+} DtqnRollout;
+/* Bytes of `state`; offsets (may be NULL): int32[DTQN_ROLLOUT_OFFSETS] byte offsets of the sections above.  < 0: bad arguments. */
+long long dtqn_rollout_state_bytes(const DtqnNet* net, const DtqnReplay* rp, const DtqnRollout* ro, int32_t* offsets);
+/* Reset every environment and start fresh contexts in block 0 (draws keyed by (seed, vstep, env)); counters are kept. */
+int dtqn_rollout_reset(const DtqnNet* net, const DtqnReplay* rp, const DtqnRollout* ro, uint32_t vstep, void* stream);
+/* One vector step.  vstep: the key of this step's draws (a count the caller never repeats); cur: the block that holds the contexts
+ * (0 after a reset, then alternating); n_max >= every live-row count: min(L, vector steps since the reset + 1).  run_forward == 0
+ * (every environment explores: epsilon >= 1, or forced): the forward is not launched.  store != 0: episodes that finish join the pending
+ * ring in environment order (store == 0: they are only counted).  authorize: the launch first writes the pending episodes numbered
+ * below min(authorize, staged) into the replay, episode k to slot (pos0 + k) mod E -- the caller passes a `staged` count it has READ
+ * from the status record, so it knows whether this launch changes the replay; authorize <= committed writes nothing.  Status granules
+ * are posted to status_host with tag vstep + 1.  train_mode / dropout_seed / dropout_step as dtqn_actor_forward_batch.  All on `stream`. */
+int dtqn_rollout_step(const DtqnNet* net, const float* theta, const DtqnReplay* rp, const DtqnRollout* ro, uint32_t vstep, int cur,
+                      int n_max, float epsilon, int store, long long authorize, int run_forward, int train_mode, uint32_t dropout_seed,
+                      uint32_t dropout_step, void* stream);
+/* The commit half alone: pending episodes below min(authorize, staged) -> the replay; posts the status record with tag vstep + 1. */
+int dtqn_rollout_commit(const DtqnNet* net, const DtqnReplay* rp, const DtqnRollout* ro, uint32_t vstep, long long authorize, void* stream);
+/* Copy the whole state to / from host memory (asynchronous on `stream`; pinned memory keeps it so). */
+int dtqn_rollout_get_state(const DtqnNet* net, const DtqnReplay* rp, const DtqnRollout* ro, void* host, void* stream);
+int dtqn_rollout_set_state(const DtqnNet* net, const DtqnReplay* rp, const DtqnRollout* ro, const void* host, void* stream);
 /* DTQN.forward with the bag arguments (dtqn.py:158-218 incl. :201-214): bag_obs [B][bag_size][O] f32, bag_actions [B][bag_size] u8
  * (NULL when action_dim == 0).  Row-block tiled path; workspace as dtqn_forward_tiled.
  * train_mode != 0 with net->dropout > 0: a train-mode forward (the reference's policy network stays in train mode while the agent

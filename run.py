@@ -72,6 +72,10 @@ def get_args(argv: Optional[Sequence[str]] = None):
                    help="host environments per learner (vectorised rollout): N > 1 steps N environments per vector step with ONE "
                         "batched actor launch and keeps the reference's 1 env step : 1 update ratio by running N updates per "
                         "vector step (all N actions of a vector step come from the same parameters)")
+    p.add_argument("--device-envs", type=int, default=0,
+                   help="device-resident rollout (dtqn_amd.agents.device_rollout.DeviceVectorActor): N > 0 steps N CarFlag / Memory "
+                        "environments on the GPU behind the batched actor forward, prepopulation included; the loop is that of "
+                        "--num-envs (N updates per vector step).  Needs --sampler device; 0 = off")
     p.add_argument("--overlap", action="store_true",
                    help="pipeline the actor forward of step t+1 with TD update t+1 on two HIP streams (same policy-vs-action "
                         "semantics; an episode that ends at step t becomes sampleable one update later)")
@@ -210,6 +214,8 @@ def train(agent, envs, eval_envs, env_strs, total_steps, eps, eval_frequency, ev
             if stop:
                 if is_main:
                     print(f"Reached time limit. Saving checkpoint with {agent.num_train_steps} steps completed.")
+                if hasattr(vector, "sync"):
+                    vector.sync()                  # device-resident rollout: the host's view of the replay, exact again
                 # every rank writes: rank 0 the full checkpoint, replicas their replay shard and RNG streams
                 agent.save_checkpoint(policy_path, None, mean_success_rate, mean_reward, mean_episode_length, eps)
                 return
@@ -245,6 +251,23 @@ def run_experiment(args):
         raise NotImplementedError("--render is outside dtqn_amd's scope")
     if args.eval_envs < 1:
         raise ValueError("--eval-envs must be at least 1")
+    vector = None
+    if args.device_envs < 0:
+        raise ValueError("--device-envs must not be negative")
+    if args.device_envs > 0:
+        if args.num_envs > 1:
+            raise ValueError("--device-envs and --num-envs > 1 exclude each other: the environments live on the device or on the host")
+        if args.overlap:
+            raise ValueError("--device-envs does not combine with --overlap (there is no host-side actor forward to overlap)")
+        if world > 1:
+            raise NotImplementedError("--device-envs: data-parallel runs are not covered")
+        if len(args.envs) != 1:
+            raise NotImplementedError("--device-envs steps copies of ONE training domain")
+        from dtqn_amd.agents.device_rollout import DeviceVectorActor
+        # the step cap is the registry entry's; an explicit --max-episode-steps (it sizes the replay's rows) caps the device
+        # environments as well, so that an episode always fits its slot
+        vector = DeviceVectorActor(agent, args.envs[0], args.device_envs, args.seed + 1000 * (rank + 1),
+                                   max_episode_steps=args.max_episode_steps if args.max_episode_steps > 0 else None)
     if os.path.exists(policy_path + "_mini_checkpoint.pt"):
         done_steps = agent.load_mini_checkpoint(policy_path)["step"]
         print(f"Found a mini checkpoint that completed {done_steps} training steps.")
@@ -255,13 +278,17 @@ def run_experiment(args):
             raise SystemExit(0)
         wandb_id, mean_success_rate, mean_reward, mean_episode_length, eps.val = agent.load_checkpoint(policy_path)
         wandb_kwargs = {"resume": "must", "id": wandb_id}
+        if vector is not None:
+            vector.attach()                        # the restored replay's position is where the next finished episode goes
     else:
         wandb_kwargs = {"resume": None}
-        prepopulate(agent, args.prepopulate, envs)
+        if vector is not None:
+            vector.prepopulate(args.prepopulate)
+        else:
+            prepopulate(agent, args.prepopulate, envs)
         mean_success_rate, mean_reward, mean_episode_length = RunningAverage(10), RunningAverage(10), RunningAverage(10)
     logger = get_logger(policy_path, args, wandb_kwargs) if is_main else None
     time_remaining = args.time_limit * 3600 - (time() - start) if args.time_limit else None
-    vector = None
     if args.num_envs > 1:
         from dtqn_amd.agents.vector import VectorActor
         # N copies of the (first) training domain, each with its own seed
@@ -282,6 +309,8 @@ def run_experiment(args):
     train(agent, envs, eval_envs, args.envs, args.num_steps, eps, args.eval_frequency, args.eval_episodes, policy_path,
           args.save_policy, logger, mean_success_rate, mean_reward, mean_episode_length, time_remaining, args.verbose, is_main,
           overlap=args.overlap, vector=vector, evaluators=evaluators)
+    if hasattr(vector, "sync"):
+        vector.sync()
     if is_main:
         agent.save_mini_checkpoint(checkpoint_dir=policy_path, wandb_id=None)
     return agent
