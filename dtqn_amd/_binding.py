@@ -74,6 +74,7 @@ DtqnReplay = _make("DtqnReplay")
 DtqnReplayRecord = _make("DtqnReplayRecord")
 DtqnTd = _make("DtqnTd")
 DtqnRollout = _make("DtqnRollout")
+DtqnEval = _make("DtqnEval")
 
 
 def load_library(path: str) -> ctypes.CDLL:
@@ -108,6 +109,11 @@ def load_library(path: str) -> ctypes.CDLL:
         "dtqn_rollout_commit": [P(DtqnNet), P(DtqnReplay), P(DtqnRollout), u32, ctypes.c_longlong, vp],
         "dtqn_rollout_get_state": [P(DtqnNet), P(DtqnReplay), P(DtqnRollout), vp, vp],
         "dtqn_rollout_set_state": [P(DtqnNet), P(DtqnReplay), P(DtqnRollout), vp, vp],
+        "dtqn_deval_state_bytes": [P(DtqnNet), P(DtqnEval), vp],
+        "dtqn_deval_begin": [P(DtqnNet), P(DtqnEval), u32, i32, vp],
+        "dtqn_deval_step": [P(DtqnNet), vp, P(DtqnEval), u32, u32, i32, i32, i32, vp],
+        "dtqn_deval_get_state": [P(DtqnNet), P(DtqnEval), vp, vp],
+        "dtqn_deval_set_state": [P(DtqnNet), P(DtqnEval), vp, vp],
         "dtqn_forward_tiled_strided": [P(DtqnNet), vp, vp, vp, i32, i32, i32, vp, vp, vp],
         "dtqn_forward_bag": [P(DtqnNet), vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, u32, u32, vp],
         "dtqn_forward": [P(DtqnNet), vp, vp, vp, i32, i32, vp, vp],
@@ -169,7 +175,8 @@ def load_library(path: str) -> ctypes.CDLL:
         fn.restype = ctypes.c_char_p if name == "dtqn_build_info" else (
             ctypes.c_longlong if name in ("dtqn_img_act_floats", "dtqn_img_gact_floats", "dtqn_img_wpart_floats",
                                                     "dtqn_grad_workspace_floats", "dtqn_img_actor_stage_bytes",
-                                                    "dtqn_img_actor_workspace_floats", "dtqn_rollout_state_bytes") else ctypes.c_int)
+                                                    "dtqn_img_actor_workspace_floats", "dtqn_rollout_state_bytes",
+                                                    "dtqn_deval_state_bytes") else ctypes.c_int)
     assert set(protos) == set(FUNCTIONS), sorted(set(protos) ^ set(FUNCTIONS))
     if lib.dtqn_abi_version() != DEFINES["DTQN_ABI_VERSION"]:
         raise OSError(f"{path}: ABI version {lib.dtqn_abi_version()} != header {DEFINES['DTQN_ABI_VERSION']}")

@@ -4,6 +4,7 @@
 #include <cstdlib>
 
 #include "dtqn_actor.hpp"
+#include "dtqn_deval.hpp"
 #include "dtqn_hip.h"
 #include "dtqn_limits.h"
 #include "dtqn_rollout.hpp"
@@ -274,6 +275,23 @@ extern "C" int dtqn_rollout_step(const DtqnNet* net, const float* theta, const D
         if (rc != DTQN_OK) return rc;
     }
     return dtqn::rollout_step_launch(net, rp, ro, vstep, cur, n_max, epsilon, store, authorize, run_forward ? 1 : 0, (hipStream_t)stream);
+}
+
+// Device-resident evaluation (dtqn_deval.hip): the same forward in eval mode (no dropout key is taken) on the context block that lives
+// in the evaluation state, then the one-workgroup step kernel.  Two launches, nothing between.
+extern "C" int dtqn_deval_step(const DtqnNet* net, const float* theta, const DtqnEval* ev, uint32_t key, uint32_t step, int cur, int n_max,
+                               int episodes, void* stream) {
+    int rc = dtqn::deval_check(net, ev);
+    if (rc != DTQN_OK) return rc;
+    if (cur != 0 && cur != 1) return DTQN_ERR_ARG;
+    if (episodes < 0 || episodes > ev->max_episodes) return DTQN_ERR_ARG;
+    if (!theta || !ev->q_dev || (!net->tiled && !ev->q_last)) return DTQN_ERR_ARG;
+    if (n_max < 1 || n_max > net->ctx_len) return DTQN_ERR_ARG;                 // dtqn.py:170-173
+    const dtqn::DevalLayout l = dtqn::deval_layout(net, ev);
+    const ActorBlock b = actor_block(net, static_cast<uint8_t*>(ev->state) + l.off[8 + cur], ev->n_envs);
+    rc = actor_batch_forward(net, theta, b, ev->n_envs, ev->n_envs, n_max, ev->q_dev, ev->q_last, ev->workspace, 0, 0u, 0u, stream);
+    if (rc != DTQN_OK) return rc;
+    return dtqn::deval_step_launch(net, ev, key, step, cur, n_max, episodes, (hipStream_t)stream);
 }
 
 // The differentiable forward without dropout (the function the no-grad forward computes): the _drop entry points with the masks off.

@@ -62,40 +62,21 @@ constexpr uint32_t kDrawCard = 40;         // Memory: the next shown card
 constexpr uint32_t kDrawPad = 41;          // the action of context row 0 (Context.reset fills its action rows with random draws)
 constexpr uint32_t kDrawResetAll = 64;     // dtqn_rollout_reset: a range of its own (a step with the same vstep may reset too)
 
-constexpr double kMaxPosition = 1.1, kMaxSpeed = 0.07, kPower = 0.0015, kPriest = 0.5, kPriestDelta = 0.2;
-
 // The first observation of a fresh episode -> staging row 0 and context row 0 of the block a step writes; environment state.
 __device__ __forceinline__ void rollout_reset_env(const RolloutArgs& a, int i, uint32_t base) {
     const int O = a.O, L = a.L, T = a.rp.max_steps;
     float* srow = a.stage_obs + (size_t)i * (T + 1) * O;
     float* crow = a.obs_out + (size_t)i * L * O;
     if (a.kind == DTQN_ROLLOUT_CARFLAG) {
-        // car_flag.py:31-37: the side first, then the start position, uniform on [-0.2, 0.2) from 53 random bits
-        const bool right = (hash_u32(a.seed, a.vstep, (uint32_t)i, base) >> 31) == 0u;
-        const unsigned long long bits = ((unsigned long long)(hash_u32(a.seed, a.vstep, (uint32_t)i, base + 1) >> 5) << 26) |
-                                        (unsigned long long)(hash_u32(a.seed, a.vstep, (uint32_t)i, base + 2) >> 6);
-        const double u = (double)bits * (1.0 / 9007199254740992.0);
         double* s = a.env_f64 + (size_t)i * 4;
-        s[0] = -0.2 + 0.4 * u;
-        s[1] = 0.0;
-        s[2] = 0.0;
-        s[3] = right ? 1.0 : -1.0;
+        rollout_carflag_reset(s, hash_u32(a.seed, a.vstep, (uint32_t)i, base), hash_u32(a.seed, a.vstep, (uint32_t)i, base + 1),
+                              hash_u32(a.seed, a.vstep, (uint32_t)i, base + 2));
         for (int k = 0; k < 3; ++k) srow[k] = crow[k] = (float)s[k];
     } else {
-        // memory_cards.py:29-35: the pairs in order, Fisher-Yates, every card hidden, then the first shown card
         const int C = 2 * a.pairs;
         int32_t* e = a.env_i32 + (size_t)i * kRolloutEnvInts;
-        int32_t *hidden = e + 1, *shown = e + 1 + C;
-        for (int k = 0; k < C; ++k) { hidden[k] = 1 + k / 2; shown[k] = 0; }
-        for (int k = C - 1; k > 0; --k) {
-            const int j = (int)(rollout_u(a.seed, a.vstep, i, base + (uint32_t)k) * (double)(k + 1));
-            const int32_t t = hidden[k];
-            hidden[k] = hidden[j];
-            hidden[j] = t;
-        }
-        const int cur = (int)(rollout_u(a.seed, a.vstep, i, base + (uint32_t)C) * (double)C);
-        e[0] = cur;
-        shown[cur] = hidden[cur];
+        rollout_memory_reset(e, a.pairs, [&](int k) { return rollout_u(a.seed, a.vstep, i, base + (uint32_t)k); });
+        const int32_t* shown = e + 1 + C;
         for (int k = 0; k < C; ++k) srow[k] = crow[k] = (float)shown[k];
     }
     a.act_out[(size_t)i * L] = (uint8_t)(int)(rollout_u(a.seed, a.vstep, i, base + kDrawPad) * (double)a.A);
@@ -108,74 +89,6 @@ __global__ __launch_bounds__(DTQN_THREADS) void dtqn_rollout_reset_kernel(Rollou
     for (int i = (int)threadIdx.x; i < a.n_envs; i += DTQN_THREADS) {
         rollout_reset_env(a, i, kDrawResetAll);
         for (int k = 0; k < kRolloutLastInts; ++k) a.last[(size_t)i * kRolloutLastInts + k] = 0;
-    }
-}
-
-// CarFlag.step (car_flag.py:39-62) in float64, statement by statement.  No contraction: each Python statement rounds once per
-// operation.  (force is -1, 0 or 1, so force * POWER is exact and velocity + force * POWER rounds once either way; the pragma keeps
-// that true of every other expression here as well.)
-__device__ __forceinline__ void rollout_carflag_step(double* s, int action, double& reward, bool& done, bool& success) {
-#pragma clang fp contract(off)
-    double position = s[0], velocity = s[1];
-    const double heaven = s[3], hell = -s[3];
-    const double force = (double)(action - 1);
-    velocity = velocity + force * kPower;
-    velocity = velocity > -kMaxSpeed ? velocity : -kMaxSpeed;            // max(v, -MAX_SPEED), then min(., MAX_SPEED)
-    velocity = velocity < kMaxSpeed ? velocity : kMaxSpeed;
-    position = position + velocity;
-    position = position > -kMaxPosition ? position : -kMaxPosition;
-    position = position < kMaxPosition ? position : kMaxPosition;
-    if (position == -kMaxPosition && velocity < 0.0) velocity = 0.0;
-    done = position >= 1.0 || position <= -1.0;
-    reward = 0.0;
-    if (heaven > hell) {
-        if (position >= heaven) reward = 1.0;
-        if (position <= hell) reward = -1.0;
-    } else {
-        if (position <= heaven) reward = 1.0;
-        if (position >= hell) reward = -1.0;
-    }
-    double direction = 0.0;
-    if (kPriest - kPriestDelta <= position && position <= kPriest + kPriestDelta) direction = heaven > hell ? 1.0 : -1.0;
-    s[0] = position;
-    s[1] = velocity;
-    s[2] = direction;
-    success = reward > 0.0;
-}
-
-// Memory.step (memory_cards.py:37-58).  A card that has left the table still "matches" when its hidden value equals the shown one:
-// the comparison is against the hidden values, as in the reference.  The next shown card is the k-th card still on the table, k
-// uniform: the distribution of the host's rejection loop without its unbounded loop.
-__device__ __forceinline__ void rollout_memory_step(const RolloutArgs& a, int i, int action, double& reward, bool& done, bool& success) {
-    const int C = 2 * a.pairs, removed = a.pairs + 1;
-    int32_t* e = a.env_i32 + (size_t)i * kRolloutEnvInts;
-    int32_t *hidden = e + 1, *shown = e + 1 + C;
-    const int cur = e[0] < 0 ? 0 : (e[0] < C ? e[0] : C - 1);
-    done = false;
-    success = false;
-    if (action != cur && hidden[action] == shown[cur]) {
-        shown[action] = removed;
-        shown[cur] = removed;
-        reward = 0.0;
-        int left = 0;
-        for (int k = 0; k < C; ++k) left += shown[k] != removed ? 1 : 0;
-        if (left == 0) done = success = true;
-    } else {
-        shown[cur] = 0;
-        reward = -1.0;
-    }
-    if (!done) {
-        int left = 0;
-        for (int k = 0; k < C; ++k) left += shown[k] != removed ? 1 : 0;
-        int pick = (int)(rollout_u(a.seed, a.vstep, i, kDrawCard) * (double)left);
-        int next = 0;
-        for (int k = 0; k < C; ++k)
-            if (shown[k] != removed) {
-                if (pick == 0) next = k;
-                --pick;
-            }
-        e[0] = next;
-        shown[next] = hidden[next];
     }
 }
 
@@ -251,7 +164,7 @@ __global__ __launch_bounds__(DTQN_THREADS) void dtqn_rollout_step_kernel(Rollout
         double reward;
         bool done, success;
         if (a.kind == DTQN_ROLLOUT_CARFLAG) rollout_carflag_step(a.env_f64 + (size_t)i * 4, action, reward, done, success);
-        else rollout_memory_step(a, i, action, reward, done, success);
+        else rollout_memory_step(a.env_i32 + (size_t)i * kRolloutEnvInts, a.pairs, action, rollout_u(a.seed, a.vstep, i, kDrawCard), reward, done, success);
         // gym TimeLimit (time_limit.py): the cap ends the episode; a truncated step is stored as not done (run.py:113)
         const int steps = t + 1;
         bool truncated = false;

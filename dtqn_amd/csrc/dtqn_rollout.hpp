@@ -1,4 +1,5 @@
-// Device-resident rollout: the layout of its one state allocation and the launches dtqn_api.cpp sequences (dtqn_rollout.hip).
+// Device-resident rollout: the layout of its one state allocation and the launches dtqn_api.cpp sequences (dtqn_rollout.hip), and
+// the one copy of the environment arithmetic: the rollout and the device-resident evaluation (dtqn_deval.hip) both step with it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,6 +11,106 @@ namespace dtqn {
 constexpr int kRolloutEnvInts = 40;        // Memory: current card | hidden values [cards] | shown table [cards], cards <= 16
 constexpr int kRolloutLastInts = 8;
 constexpr int kRolloutCounters = 8;
+
+// ---- environment arithmetic (plain pointers in, the uniform draws handed over by the caller: no key scheme in here) ----------------
+constexpr double kMaxPosition = 1.1, kMaxSpeed = 0.07, kPower = 0.0015, kPriest = 0.5, kPriestDelta = 0.2;
+
+// CarFlag.reset (car_flag.py:31-37): the side first (top bit of h_side), then the start position, uniform on [-0.2, 0.2) from the 53
+// random bits of (h_hi >> 5, h_lo >> 6).  s: position, velocity, direction, heaven position.
+__device__ __forceinline__ void rollout_carflag_reset(double* s, uint32_t h_side, uint32_t h_hi, uint32_t h_lo) {
+    const bool right = (h_side >> 31) == 0u;
+    const unsigned long long bits = ((unsigned long long)(h_hi >> 5) << 26) | (unsigned long long)(h_lo >> 6);
+    const double u = (double)bits * (1.0 / 9007199254740992.0);
+    s[0] = -0.2 + 0.4 * u;
+    s[1] = 0.0;
+    s[2] = 0.0;
+    s[3] = right ? 1.0 : -1.0;
+}
+
+// Memory.reset (memory_cards.py:29-35): the pairs in order, Fisher-Yates, every card hidden, then the first shown card.
+// e: current card | hidden values [cards] | shown table [cards]; u(k) in [0, 1): draw k -- k = cards - 1 .. 1 the shuffle, k = cards the card.
+template <class Draw>
+__device__ __forceinline__ void rollout_memory_reset(int32_t* e, int pairs, Draw&& u) {
+    const int C = 2 * pairs;
+    int32_t *hidden = e + 1, *shown = e + 1 + C;
+    for (int k = 0; k < C; ++k) { hidden[k] = 1 + k / 2; shown[k] = 0; }
+    for (int k = C - 1; k > 0; --k) {
+        const int j = (int)(u(k) * (double)(k + 1));
+        const int32_t t = hidden[k];
+        hidden[k] = hidden[j];
+        hidden[j] = t;
+    }
+    const int cur = (int)(u(C) * (double)C);
+    e[0] = cur;
+    shown[cur] = hidden[cur];
+}
+
+// CarFlag.step (car_flag.py:39-62) in float64, statement by statement.  No contraction: each Python statement rounds once per
+// operation.  (force is -1, 0 or 1, so force * POWER is exact and velocity + force * POWER rounds once either way; the pragma keeps
+// that true of every other expression here as well.)
+__device__ __forceinline__ void rollout_carflag_step(double* s, int action, double& reward, bool& done, bool& success) {
+#pragma clang fp contract(off)
+    double position = s[0], velocity = s[1];
+    const double heaven = s[3], hell = -s[3];
+    const double force = (double)(action - 1);
+    velocity = velocity + force * kPower;
+    velocity = velocity > -kMaxSpeed ? velocity : -kMaxSpeed;            // max(v, -MAX_SPEED), then min(., MAX_SPEED)
+    velocity = velocity < kMaxSpeed ? velocity : kMaxSpeed;
+    position = position + velocity;
+    position = position > -kMaxPosition ? position : -kMaxPosition;
+    position = position < kMaxPosition ? position : kMaxPosition;
+    if (position == -kMaxPosition && velocity < 0.0) velocity = 0.0;
+    done = position >= 1.0 || position <= -1.0;
+    reward = 0.0;
+    if (heaven > hell) {
+        if (position >= heaven) reward = 1.0;
+        if (position <= hell) reward = -1.0;
+    } else {
+        if (position <= heaven) reward = 1.0;
+        if (position >= hell) reward = -1.0;
+    }
+    double direction = 0.0;
+    if (kPriest - kPriestDelta <= position && position <= kPriest + kPriestDelta) direction = heaven > hell ? 1.0 : -1.0;
+    s[0] = position;
+    s[1] = velocity;
+    s[2] = direction;
+    success = reward > 0.0;
+}
+
+// Memory.step (memory_cards.py:37-58).  A card that has left the table still "matches" when its hidden value equals the shown one:
+// the comparison is against the hidden values, as in the reference.  The next shown card is the k-th card still on the table, k
+// uniform (u_card in [0, 1)): the distribution of the host's rejection loop without its unbounded loop.
+__device__ __forceinline__ void rollout_memory_step(int32_t* e, int pairs, int action, double u_card, double& reward, bool& done, bool& success) {
+    const int C = 2 * pairs, removed = pairs + 1;
+    int32_t *hidden = e + 1, *shown = e + 1 + C;
+    const int cur = e[0] < 0 ? 0 : (e[0] < C ? e[0] : C - 1);
+    done = false;
+    success = false;
+    if (action != cur && hidden[action] == shown[cur]) {
+        shown[action] = removed;
+        shown[cur] = removed;
+        reward = 0.0;
+        int left = 0;
+        for (int k = 0; k < C; ++k) left += shown[k] != removed ? 1 : 0;
+        if (left == 0) done = success = true;
+    } else {
+        shown[cur] = 0;
+        reward = -1.0;
+    }
+    if (!done) {
+        int left = 0;
+        for (int k = 0; k < C; ++k) left += shown[k] != removed ? 1 : 0;
+        int pick = (int)(u_card * (double)left);
+        int next = 0;
+        for (int k = 0; k < C; ++k)
+            if (shown[k] != removed) {
+                if (pick == 0) next = k;
+                --pick;
+            }
+        e[0] = next;
+        shown[next] = hidden[next];
+    }
+}
 
 // Byte offsets of the sections of DtqnRollout::state (include/dtqn_hip.h lists them), every section 16-byte aligned.
 struct RolloutLayout {

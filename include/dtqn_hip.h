@@ -443,6 +443,56 @@ int dtqn_rollout_commit(const DtqnNet* net, const DtqnReplay* rp, const DtqnRoll
 /* Copy the whole state to / from host memory (asynchronous on `stream`; pinned memory keeps it so). */
 int dtqn_rollout_get_state(const DtqnNet* net, const DtqnReplay* rp, const DtqnRollout* ro, void* host, void* stream);
 int dtqn_rollout_set_state(const DtqnNet* net, const DtqnReplay* rp, const DtqnRollout* ro, const void* host, void* stream);
+/* ------------------------------------------------------------------------------------------
+ * Device-resident greedy evaluation (dtqn_deval.hip; DESIGN.md "Device-resident evaluation"): a quota of `episodes` greedy episodes
+ * played by N CarFlag or Memory environments in ONE device allocation (`state`).  Environment i plays episodes i, i + N, ...; with
+ * none left it goes idle (len = 1, no step, never counted).  Every draw of an episode is a function of (seed, key, episode index,
+ * step within the episode, draw kind): the same episode whatever N plays it.
+ * state layout (byte offsets from dtqn_deval_state_bytes; O = obs_dim, L = ctx_len, A = num_actions, K = max_episodes):
+ *   [0] counters  i64[8]      episodes finished | env steps | successes | length sum | return sum (f64) | environments still playing |
+ *                             vector steps of this evaluation | 0
+ *   [1] env_f64   f64[N][4]   CarFlag: position, velocity, direction, heaven position (+1 / -1)
+ *   [2] env_i32   i32[N][40]  Memory: current card | hidden values [cards] | shown table [cards]
+ *   [3] elapsed   i32[N]      steps of the episode in progress (= the context's timestep)
+ *   [4] ep_ret    f64[N]      its return so far
+ *   [5] episode   i32[N]      index of the episode in progress, -1 = idle
+ *   [6] last      i32[N][8]   last step: action (-1 idle) | 0 | done | done and not truncated | truncated | environment's success |
+ *                             episode stepped (-1 idle) | reward (f32 bits)
+ *   [7] obs_new   f32[N][O]   the observation the last step returned
+ *   [8] block 0, [9] block 1  the packed actor block of dtqn_actor_forward_batch, twice (a step reads one and writes the other)
+ *   [10] results  [K] rows of 24 bytes, row e = episode e: f64 return | i32 length | i32 success (the environment's or return > 0) |
+ *                             i32 environment | i32 vector step it finished in
+ * ------------------------------------------------------------------------------------------ */
+#define DTQN_DEVAL_OFFSETS 11
+#define DTQN_DEVAL_STATUS_WORDS 16
+#define DTQN_DEVAL_RESULT_BYTES 24
+typedef struct DtqnEval {
+    void* state;                      /* device, dtqn_deval_state_bytes() bytes, zeroed once by the caller */
+    void* status_host;                /* PINNED: DTQN_DEVAL_STATUS_WORDS granules {word, tag} of 8 bytes, zeroed before every evaluation */
+    float* q_last;                    /* device [N][A]: Q of the last live row (whole-sequence networks write it) */
+    float* q_dev;                     /* device [N][L][A] */
+    float* workspace;                 /* as dtqn_actor_forward_batch for N */
+    int32_t env_kind;                 /* DTQN_ROLLOUT_CARFLAG / DTQN_ROLLOUT_MEMORY */
+    int32_t n_envs;
+    int32_t max_episode_steps;        /* gym TimeLimit cap */
+    int32_t num_pairs;                /* Memory: pairs on the table (1..8) */
+    int32_t max_episodes;             /* K: rows of the results table */
+    uint32_t seed;
+} DtqnEval;
+/* Bytes of `state`; offsets (may be NULL): int32[DTQN_DEVAL_OFFSETS] byte offsets of the sections above.  < 0: bad arguments. */
+long long dtqn_deval_state_bytes(const DtqnNet* net, const DtqnEval* ev, int32_t* offsets);
+/* Start an evaluation of `episodes` (0 .. max_episodes) episodes: counters and results rows zeroed, environment i < min(N, episodes)
+ * reset to episode i with a fresh context (row 0) in block 0, the others idle.  key: names the episodes (same key, same episodes).
+ * Posts the status record with a tag whose step field is 0. */
+int dtqn_deval_begin(const DtqnNet* net, const DtqnEval* ev, uint32_t key, int episodes, void* stream);
+/* One vector step: the forward of dtqn_actor_forward_batch (train_mode = 0) on block `cur` (0 after a begin, then alternating), then
+ * the one-workgroup step kernel; two launches, nothing between.  step: vector steps of this evaluation so far; n_max >= every
+ * live-row count: min(L, step + 1).  Status granules go to status_host with tag 0x40000000 | (key & 0x3fff) << 16 | (step + 1) & 0xffff. */
+int dtqn_deval_step(const DtqnNet* net, const float* theta, const DtqnEval* ev, uint32_t key, uint32_t step, int cur, int n_max,
+                    int episodes, void* stream);
+/* Copy the whole state to / from host memory (asynchronous on `stream`; pinned memory keeps it so). */
+int dtqn_deval_get_state(const DtqnNet* net, const DtqnEval* ev, void* host, void* stream);
+int dtqn_deval_set_state(const DtqnNet* net, const DtqnEval* ev, const void* host, void* stream);
 /* DTQN.forward with the bag arguments (dtqn.py:158-218 incl. :201-214): bag_obs [B][bag_size][O] f32, bag_actions [B][bag_size] u8
  * (NULL when action_dim == 0).  Row-block tiled path; workspace as dtqn_forward_tiled.
  * train_mode != 0 with net->dropout > 0: a train-mode forward (the reference's policy network stays in train mode while the agent

@@ -82,6 +82,10 @@ def get_args(argv: Optional[Sequence[str]] = None):
     p.add_argument("--eval-envs", type=int, default=1,
                    help="evaluation environments per domain: N > 1 plays the evaluation episodes N at a time through one batched greedy "
                         "launch per step (dtqn_amd.agents.vector.VectorEvaluator); 1 evaluates through the single-environment actor")
+    p.add_argument("--device-eval-envs", type=int, default=0,
+                   help="device-resident greedy evaluation (dtqn_amd.agents.device_eval.DeviceEvaluator): N > 0 plays the evaluation "
+                        "episodes of CarFlag / Memory domains N at a time on the GPU, with no host round trip per step; with or without "
+                        "--device-envs, not with --eval-envs > 1; 0 = off")
     return p.parse_args(argv)
 
 
@@ -151,7 +155,8 @@ def train(agent, envs, eval_envs, env_strs, total_steps, eps, eval_frequency, ev
     iterations only account for them), which keeps one update per env step.  The vector steps are driven by the updates still
     owed, not by `timestep % N`: a resumed run steps on its first iteration, and the time limit is only honoured at a
     vector-step boundary, so a checkpoint's `num_train_steps` always equals the loop's timestep.
-    evaluators: one VectorEvaluator per entry of env_strs (--eval-envs N > 1), used instead of evaluate() on eval_envs."""
+    evaluators: one VectorEvaluator (--eval-envs N > 1) or DeviceEvaluator (--device-eval-envs N) per entry of env_strs, used instead
+    of evaluate() on eval_envs."""
     start = time()
     agent.eval_off()
     if vector is None:
@@ -229,6 +234,13 @@ def run_experiment(args):
     rank, world, local = ddp.init_from_env("cuda" if args.device.startswith("cuda") else "cpu")
     is_main = rank == 0
     device = torch.device(args.device if world == 1 or not args.device.startswith("cuda") else f"cuda:{local}")
+    if args.device_eval_envs < 0:
+        raise ValueError("--device-eval-envs must not be negative")
+    if args.device_eval_envs > 0:
+        if args.eval_envs > 1:
+            raise ValueError("--device-eval-envs and --eval-envs > 1 exclude each other: the evaluation environments live on the device or on the host")
+        if world > 1:
+            raise NotImplementedError("--device-eval-envs: data-parallel runs are not covered")
     envs = [env_processing.make_env(e) for e in args.envs]
     eval_envs = [env_processing.make_env(e) for e in args.envs]
     set_global_seed(args.seed + rank, *(envs + eval_envs))         # per-rank env / replay / exploration streams
@@ -306,6 +318,12 @@ def run_experiment(args):
             for k, e in enumerate(copies):
                 e.seed(args.seed + 1000 * (rank + 1) + 500 + d * args.eval_envs + k)
             evaluators.append(VectorEvaluator(agent, copies, ref_quirks=args.ref_quirks))
+    if args.device_eval_envs > 0:
+        from dtqn_amd.agents.device_eval import DeviceEvaluator
+        # one evaluator per evaluation domain, seeded in a range of its own; the step cap as for --device-envs
+        evaluators = [DeviceEvaluator(agent, env_str, args.device_eval_envs, args.seed + 1000 * (rank + 1) + 700 + d,
+                                      max_episode_steps=args.max_episode_steps if args.max_episode_steps > 0 else None,
+                                      max_episodes=max(1, args.eval_episodes)) for d, env_str in enumerate(args.envs)]
     train(agent, envs, eval_envs, args.envs, args.num_steps, eps, args.eval_frequency, args.eval_episodes, policy_path,
           args.save_policy, logger, mean_success_rate, mean_reward, mean_episode_length, time_remaining, args.verbose, is_main,
           overlap=args.overlap, vector=vector, evaluators=evaluators)
