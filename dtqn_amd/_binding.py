@@ -103,6 +103,7 @@ def load_library(path: str) -> ctypes.CDLL:
         "dtqn_actor_forward_batch": [P(DtqnNet), vp, vp, vp, i32, i32, vp, vp, vp, i32, u32, u32, vp],
         "dtqn_actor_greedy_batch": [P(DtqnNet), vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, u32, u32, vp],
         "dtqn_debug_last_actor_live": [],
+        "dtqn_pomdp_table_bytes": [i32, i32, i32, vp],
         "dtqn_rollout_state_bytes": [P(DtqnNet), P(DtqnReplay), P(DtqnRollout), vp],
         "dtqn_rollout_reset": [P(DtqnNet), P(DtqnReplay), P(DtqnRollout), u32, vp],
         "dtqn_rollout_step": [P(DtqnNet), vp, P(DtqnReplay), P(DtqnRollout), u32, i32, i32, ctypes.c_float, i32, ctypes.c_longlong, i32, i32, u32, u32, vp],
@@ -175,7 +176,7 @@ def load_library(path: str) -> ctypes.CDLL:
         fn.restype = ctypes.c_char_p if name == "dtqn_build_info" else (
             ctypes.c_longlong if name in ("dtqn_img_act_floats", "dtqn_img_gact_floats", "dtqn_img_wpart_floats",
                                                     "dtqn_grad_workspace_floats", "dtqn_img_actor_stage_bytes",
-                                                    "dtqn_img_actor_workspace_floats", "dtqn_rollout_state_bytes",
+                                                    "dtqn_img_actor_workspace_floats", "dtqn_rollout_state_bytes", "dtqn_pomdp_table_bytes",
                                                     "dtqn_deval_state_bytes") else ctypes.c_int)
     assert set(protos) == set(FUNCTIONS), sorted(set(protos) ^ set(FUNCTIONS))
     if lib.dtqn_abi_version() != DEFINES["DTQN_ABI_VERSION"]:

@@ -1,4 +1,4 @@
-"""Device-resident greedy evaluation: a quota of evaluation episodes played by N CarFlag or Memory environments on the GPU.
+"""Device-resident greedy evaluation: a quota of evaluation episodes played by N CarFlag, Memory or tabular POMDP environments on the GPU.
 
 `run.evaluate` and `VectorEvaluator` (agents/vector.py) make one host round trip per environment step: a forward, an awaited read-back,
 a numpy environment step, a `Context` re-staged.  `DeviceEvaluator` keeps all of it in one device allocation (csrc/dtqn_deval.hip,
@@ -28,8 +28,7 @@ import torch
 
 from .. import _binding as B
 from .. import dist as ddp
-from .. import envs as _envs
-from .device_rollout import ENV_KINDS
+from .device_rollout import make_device_env, upload_pomdp_tables
 
 COUNTERS = ("finished", "env_steps", "successes", "length_sum", "return_sum", "live", "vector_steps", "spare")
 _STATUS_WORDS, _OFFSETS, _ROW = B.DEFINES["DTQN_DEVAL_STATUS_WORDS"], B.DEFINES["DTQN_DEVAL_OFFSETS"], B.DEFINES["DTQN_DEVAL_RESULT_BYTES"]
@@ -46,8 +45,7 @@ class DeviceEvaluator:
 
     def __init__(self, agent, env_id: str, n_envs: int, seed: int, max_episode_steps: Optional[int] = None, num_pairs: Optional[int] = None,
                  max_episodes: int = 64):
-        if env_id not in ENV_KINDS:
-            raise NotImplementedError(f"device-resident evaluation covers {sorted(ENV_KINDS)}, not {env_id!r} (use --eval-envs)")
+        env, kind = make_device_env(env_id, max_episode_steps, "evaluation (use --eval-envs otherwise)")
         if getattr(agent, "image", None) is not None:
             raise NotImplementedError("device-resident evaluation: image networks are not covered (use --eval-envs)")
         if agent.bag.size > 0:
@@ -61,7 +59,7 @@ class DeviceEvaluator:
         self.agent, self.env_id, self.n, self.seed = agent, env_id, int(n_envs), int(seed) & 0xFFFFFFFF
         eng, dev = agent.engine, agent.device
         self.L, self.O, self.A = agent.context_len, int(agent.env_obs_length), agent.num_actions
-        env = _envs.make(env_id)
+        self.kind = kind
         self.cap = int(max_episode_steps if max_episode_steps is not None else env._max_episode_steps)
         self.pairs = int(num_pairs if num_pairs is not None else getattr(env, "num_pairs", 0))
         if self.cap < 1:
@@ -79,7 +77,10 @@ class DeviceEvaluator:
         ev = self.ev = B.DtqnEval()
         ev.status_host = self._status_h.data_ptr()
         ev.q_last, ev.q_dev, ev.workspace = self._q_last.data_ptr(), self._q_d.data_ptr(), (self._ws.data_ptr() if need > 0 else None)
-        ev.env_kind, ev.n_envs, ev.max_episode_steps, ev.num_pairs = ENV_KINDS[env_id], N, self.cap, self.pairs
+        ev.env_kind, ev.n_envs, ev.max_episode_steps, ev.num_pairs = kind, N, self.cap, self.pairs
+        if kind == B.DEFINES["DTQN_ROLLOUT_POMDP"]:
+            self.env = env                               # the host twin: its model is what the device steps
+            self._tables = upload_pomdp_tables(eng.lib, ev, env, dev)
         ev.max_episodes, ev.seed = self.max_episodes, self.seed
         self._ev_ref = ctypes.byref(ev)
         offsets = (ctypes.c_int32 * _OFFSETS)()
@@ -249,7 +250,8 @@ class DeviceEvaluator:
 
     def get_state(self) -> SimpleNamespace:
         """A host copy of the whole device state as named numpy views (include/dtqn_hip.h lists the sections); `block` is the context
-        block the next step reads.  Memory: env_i32[i] = current card | hidden values | shown table."""
+        block the next step reads.  Memory: env_i32[i] = current card | hidden values | shown table.  POMDP: env_i32[i] = state |
+        observation, env_f64[i] = the recorded uniforms (u_state, u_obs of the last step | of the reset that started the episode)."""
         agent = self.agent
         lib, net = self._lib_args()
         self._check(lib.dtqn_deval_get_state(net, self._ev_ref, _ptr(self._state_h), agent.engine._stream()), "dtqn_deval_get_state")

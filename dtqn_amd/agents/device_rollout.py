@@ -1,4 +1,4 @@
-"""Device-resident rollout: N CarFlag or Memory environments stepped on the GPU behind the batched actor forward.
+"""Device-resident rollout: N CarFlag, Memory or tabular POMDP environments stepped on the GPU behind the batched actor forward.
 
 `VectorActor` (agents/vector.py) makes a round trip through Python on every vector step: N numpy environments, N `Context` objects
 re-staged and copied over, N Q rows read back after an event wait, the epsilon-greedy draw in numpy, finished episodes replayed record
@@ -43,12 +43,38 @@ LAST_FIELDS = ("action", "explored", "done", "stored_done", "truncated", "succes
 _ptr = lambda t: ctypes.c_void_p(t.data_ptr())
 
 
+def make_device_env(env_id: str, max_episode_steps: Optional[int], what: str):
+    """The host twin of the device environments -> (env, kind).  A registered id names its kind; a tabular POMDP (an id or a `.pomdp`
+    path) is recognised from the made environment: a TabularPOMDP under the TimeLimit.  Anything else is refused."""
+    if env_id in ENV_KINDS:
+        return _envs.make(env_id), ENV_KINDS[env_id]
+    if _envs.is_pomdp(env_id):
+        env = _envs.make(env_id, max_episode_steps=max_episode_steps)
+        if isinstance(getattr(env, "env", None), _envs.TabularPOMDP):
+            return env, B.DEFINES["DTQN_ROLLOUT_POMDP"]
+    raise NotImplementedError(f"device-resident {what} covers {sorted(ENV_KINDS)} and tabular POMDPs, not {env_id!r}")
+
+
+def upload_pomdp_tables(lib, desc, env, device) -> torch.Tensor:
+    """Pack the model's tables (start_cdf | T_cdf | O_cdf | R | D) at the offsets the library states, upload them once and point the
+    descriptor (DtqnRollout / DtqnEval) at them -> the tensor, which the caller keeps alive."""
+    pomdp = env.env
+    S, A, Z = pomdp.model.sizes
+    offsets = (ctypes.c_longlong * B.DEFINES["DTQN_POMDP_SECTIONS"])()
+    nbytes = int(lib.dtqn_pomdp_table_bytes(S, A, Z, offsets))
+    if nbytes <= 0:
+        raise ValueError("dtqn_pomdp_table_bytes refused this model")
+    tables = torch.from_numpy(pomdp.model.pack(list(offsets), nbytes)).to(device)
+    desc.pomdp_tables = tables.data_ptr()
+    desc.pomdp_states, desc.pomdp_actions, desc.pomdp_obs, desc.pomdp_first_obs_action = S, A, Z, pomdp.first_obs_action
+    return tables
+
+
 class DeviceVectorActor:
     RUN_AHEAD = 8                  # vector steps the host may be in front of the device; the pending ring is sized for them
 
     def __init__(self, agent, env_id: str, n_envs: int, seed: int, max_episode_steps: Optional[int] = None, num_pairs: Optional[int] = None):
-        if env_id not in ENV_KINDS:
-            raise NotImplementedError(f"device-resident rollout covers {sorted(ENV_KINDS)}, not {env_id!r} (use --num-envs)")
+        env, kind = make_device_env(env_id, max_episode_steps, "rollout (use --num-envs otherwise)")
         if getattr(agent, "image", None) is not None:
             raise NotImplementedError("device-resident rollout: image networks are not covered (use --num-envs)")
         if agent.bag.size > 0:
@@ -63,7 +89,7 @@ class DeviceVectorActor:
         self.agent, self.env_id, self.n, self.seed = agent, env_id, int(n_envs), int(seed) & 0xFFFFFFFF
         eng, rb, dev = agent.engine, agent.replay_buffer, agent.device
         self.L, self.O, self.A = agent.context_len, int(agent.env_obs_length), agent.num_actions
-        env = _envs.make(env_id)
+        self.kind = kind
         self.cap = int(max_episode_steps if max_episode_steps is not None else env._max_episode_steps)
         self.pairs = int(num_pairs if num_pairs is not None else getattr(env, "num_pairs", 0))
         if self.cap > rb.max_episode_steps:
@@ -84,7 +110,10 @@ class DeviceVectorActor:
         ro = self.ro = B.DtqnRollout()
         ro.status_host, ro.forced_actions = self._status_h.data_ptr(), self._forced.data_ptr()
         ro.q_last, ro.q_dev, ro.workspace = self._q_last.data_ptr(), self._q_d.data_ptr(), (self._ws.data_ptr() if need > 0 else None)
-        ro.env_kind, ro.n_envs, ro.max_episode_steps, ro.num_pairs = ENV_KINDS[env_id], N, self.cap, self.pairs
+        ro.env_kind, ro.n_envs, ro.max_episode_steps, ro.num_pairs = kind, N, self.cap, self.pairs
+        if kind == B.DEFINES["DTQN_ROLLOUT_POMDP"]:
+            self.env = env                               # the host twin: its model is what the device steps
+            self._tables = upload_pomdp_tables(eng.lib, ro, env, dev)
         ro.pos0, ro.seed = int(rb.pos[0]), self.seed
         ro.pending_slots = (self.RUN_AHEAD + 2) * N      # at most N episodes finish per vector step
         self.pos0 = int(rb.pos[0])
@@ -261,7 +290,8 @@ class DeviceVectorActor:
 
     def get_state(self) -> SimpleNamespace:
         """A host copy of the whole device state as named numpy views (include/dtqn_hip.h lists the sections); `block` is the context
-        block the next step reads.  Memory: env_i32[i] = current card | hidden values | shown table."""
+        block the next step reads.  Memory: env_i32[i] = current card | hidden values | shown table.  POMDP: env_i32[i] = state |
+        observation, env_f64[i] = the recorded uniforms (u_state, u_obs of the last step | of the reset that started the episode)."""
         agent = self.agent
         lib, net, rp = self._lib_args()
         self._check(lib.dtqn_rollout_get_state(net, rp, self._ro_ref, _ptr(self._state_h), agent.engine._stream()), "dtqn_rollout_get_state")

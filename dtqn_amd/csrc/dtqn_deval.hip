@@ -1,4 +1,4 @@
-// Device-resident greedy evaluation (gfx950): a quota of episodes played by N CarFlag / Memory environments behind the batched actor
+// Device-resident greedy evaluation (gfx950): a quota of episodes played by N CarFlag / Memory / tabular POMDP environments behind the batched actor
 // forward, with no host work per step.
 //
 // Replaces, per vector step, the host work of VectorEvaluator.evaluate (agents/vector.py): the awaited read-back of the greedy
@@ -43,11 +43,14 @@ struct DevalArgs {
     int kind, n_envs, cap, pairs, episodes;
     int L, O, A;
     uint32_t seed, key, step;
+    PomdpTables pomdp;                 // DTQN_ROLLOUT_POMDP: the packed tables
 };
 
 constexpr uint32_t kDevalMix = 0xE7A1u;    // (seed, key) -> the seed of this evaluation's draws
 constexpr uint32_t kDevalReset = 0;        // step 0 of an episode: CarFlag side, position (2 draws); Memory shuffle and first card (<= 17)
 constexpr uint32_t kDevalCard = 40;        // Memory: the card shown after step t
+constexpr uint32_t kDevalPomdpState = 48;  // tabular POMDP: the next state and observation of step t (its reset: kDevalReset, + 1 at step 0)
+constexpr uint32_t kDevalPomdpObs = 49;
 constexpr uint32_t kDevalPad = 41;         // the action of context row 0 (Context.reset fills its action rows with random draws)
 
 __device__ __forceinline__ uint32_t deval_seed(const DevalArgs& a) { return hash_u32(a.seed, a.key, 0u, kDevalMix); }
@@ -63,6 +66,8 @@ __device__ __forceinline__ void deval_write_obs(const DevalArgs& a, int i, float
     if (a.kind == DTQN_ROLLOUT_CARFLAG) {
         const double* s = a.env_f64 + (size_t)i * 4;
         for (int k = 0; k < 3; ++k) dst[k] = (float)s[k];             // f32 only where the observation is stored
+    } else if (a.kind == DTQN_ROLLOUT_POMDP) {
+        dst[0] = (float)a.env_i32[(size_t)i * kRolloutEnvInts + 1];
     } else {
         const int32_t* shown = a.env_i32 + (size_t)i * kRolloutEnvInts + 1 + 2 * a.pairs;
         for (int k = 0; k < a.O; ++k) dst[k] = (float)shown[k];
@@ -76,7 +81,13 @@ __device__ __forceinline__ void deval_start_episode(const DevalArgs& a, int i, i
     if (a.kind == DTQN_ROLLOUT_CARFLAG)
         rollout_carflag_reset(a.env_f64 + (size_t)i * 4, hash_u32(s, 0u, e, kDevalReset), hash_u32(s, 0u, e, kDevalReset + 1),
                               hash_u32(s, 0u, e, kDevalReset + 2));
-    else
+    else if (a.kind == DTQN_ROLLOUT_POMDP) {
+        double* rec = a.env_f64 + (size_t)i * 4;                      // the draws, recorded: [2], [3] those of this reset
+        const double u_state = deval_u(s, 0, episode, kDevalReset), u_obs = deval_u(s, 0, episode, kDevalReset + 1);
+        rollout_pomdp_reset(a.env_i32 + (size_t)i * kRolloutEnvInts, a.pomdp, u_state, u_obs);
+        rec[2] = u_state;
+        rec[3] = u_obs;
+    } else
         rollout_memory_reset(a.env_i32 + (size_t)i * kRolloutEnvInts, a.pairs, [&](int k) { return deval_u(s, 0, episode, kDevalReset + (uint32_t)k); });
     deval_write_obs(a, i, a.obs_out + (size_t)i * a.L * a.O);
     a.act_out[(size_t)i * a.L] = (uint8_t)(int)(deval_u(s, 0, episode, kDevalPad) * (double)a.A);
@@ -150,8 +161,18 @@ __global__ __launch_bounds__(DTQN_THREADS) void dtqn_deval_step_kernel(DevalArgs
         }
         double reward;
         bool done, success;
-        if (a.kind == DTQN_ROLLOUT_CARFLAG) rollout_carflag_step(a.env_f64 + (size_t)i * 4, action, reward, done, success);
-        else rollout_memory_step(a.env_i32 + (size_t)i * kRolloutEnvInts, a.pairs, action, deval_u(deval_seed(a), t, episode, kDevalCard), reward, done, success);
+        if (a.kind == DTQN_ROLLOUT_CARFLAG) {
+            rollout_carflag_step(a.env_f64 + (size_t)i * 4, action, reward, done, success);
+        } else if (a.kind == DTQN_ROLLOUT_POMDP) {
+            double* rec = a.env_f64 + (size_t)i * 4;                  // the draws, recorded: [0], [1] those of this step
+            const uint32_t s = deval_seed(a);
+            const double u_state = deval_u(s, t, episode, kDevalPomdpState), u_obs = deval_u(s, t, episode, kDevalPomdpObs);
+            rollout_pomdp_step(a.env_i32 + (size_t)i * kRolloutEnvInts, a.pomdp, action, u_state, u_obs, reward, done, success);
+            rec[0] = u_state;
+            rec[1] = u_obs;
+        } else {
+            rollout_memory_step(a.env_i32 + (size_t)i * kRolloutEnvInts, a.pairs, action, deval_u(deval_seed(a), t, episode, kDevalCard), reward, done, success);
+        }
         // gym TimeLimit (time_limit.py): the cap ends the episode; a truncated step counts as not done in the context
         const int steps = t + 1;
         bool truncated = false;
@@ -260,6 +281,8 @@ static DevalArgs deval_args(const DtqnNet* net, const DtqnEval* ev, uint32_t key
     a.kind = ev->env_kind; a.n_envs = ev->n_envs; a.cap = ev->max_episode_steps; a.pairs = ev->num_pairs; a.episodes = episodes;
     a.L = net->ctx_len; a.O = net->obs_dim; a.A = net->num_actions;
     a.seed = ev->seed; a.key = key;
+    if (ev->env_kind == DTQN_ROLLOUT_POMDP)
+        a.pomdp = pomdp_tables(ev->pomdp_tables, ev->pomdp_states, ev->pomdp_actions, ev->pomdp_obs, ev->pomdp_first_obs_action);
     return a;
 }
 
@@ -272,6 +295,9 @@ int deval_check(const DtqnNet* net, const DtqnEval* ev) {
     } else if (ev->env_kind == DTQN_ROLLOUT_MEMORY) {
         if (ev->num_pairs < 1 || 1 + 4 * ev->num_pairs > kRolloutEnvInts) return DTQN_ERR_ARG;
         if (net->obs_dim != 2 * ev->num_pairs || net->num_actions != 2 * ev->num_pairs) return DTQN_ERR_ARG;
+    } else if (ev->env_kind == DTQN_ROLLOUT_POMDP) {
+        if (pomdp_check(net, ev->pomdp_tables, ev->pomdp_states, ev->pomdp_obs, ev->pomdp_first_obs_action) != DTQN_OK) return DTQN_ERR_ARG;
+        if (net->num_actions != ev->pomdp_actions) return DTQN_ERR_ARG;
     } else {
         return DTQN_ERR_ARG;
     }

@@ -1,4 +1,4 @@
-// Device-resident rollout (gfx950): N CarFlag / Memory environments stepped behind the batched actor forward.
+// Device-resident rollout (gfx950): N CarFlag / Memory / tabular POMDP environments stepped behind the batched actor forward.
 //
 // Replaces, per vector step, the host work of VectorActor.step_all (agents/vector.py): the epsilon-greedy draw, N numpy environment
 // steps, N Context.add_transition calls with their re-staging, and the record-by-record replay of finished episodes through
@@ -47,6 +47,7 @@ struct RolloutArgs {
     int L, O, A;
     uint32_t seed, vstep, draw_base;
     float epsilon;
+    PomdpTables pomdp;                 // DTQN_ROLLOUT_POMDP: the packed tables
 };
 
 // u in [0, 1) from 32 counter-based bits, in DOUBLE: hash * 2^-32 is exact there; in f32 it can round up to 1.0
@@ -60,6 +61,8 @@ __device__ __forceinline__ long long rollout_bits(double d) { long long b; __bui
 constexpr uint32_t kDrawReset = 2;         // draws 0 / 1: explore, random action; 2 ..: the reset of a finished episode
 constexpr uint32_t kDrawCard = 40;         // Memory: the next shown card
 constexpr uint32_t kDrawPad = 41;          // the action of context row 0 (Context.reset fills its action rows with random draws)
+constexpr uint32_t kDrawPomdpState = 48;   // tabular POMDP: the step's next state and observation (its reset: base, base + 1)
+constexpr uint32_t kDrawPomdpObs = 49;
 constexpr uint32_t kDrawResetAll = 64;     // dtqn_rollout_reset: a range of its own (a step with the same vstep may reset too)
 
 // The first observation of a fresh episode -> staging row 0 and context row 0 of the block a step writes; environment state.
@@ -72,6 +75,14 @@ __device__ __forceinline__ void rollout_reset_env(const RolloutArgs& a, int i, u
         rollout_carflag_reset(s, hash_u32(a.seed, a.vstep, (uint32_t)i, base), hash_u32(a.seed, a.vstep, (uint32_t)i, base + 1),
                               hash_u32(a.seed, a.vstep, (uint32_t)i, base + 2));
         for (int k = 0; k < 3; ++k) srow[k] = crow[k] = (float)s[k];
+    } else if (a.kind == DTQN_ROLLOUT_POMDP) {
+        int32_t* e = a.env_i32 + (size_t)i * kRolloutEnvInts;
+        double* rec = a.env_f64 + (size_t)i * 4;                      // the draws, recorded: [2], [3] those of this reset
+        const double u_state = rollout_u(a.seed, a.vstep, i, base), u_obs = rollout_u(a.seed, a.vstep, i, base + 1);
+        rollout_pomdp_reset(e, a.pomdp, u_state, u_obs);
+        rec[2] = u_state;
+        rec[3] = u_obs;
+        srow[0] = crow[0] = (float)e[1];
     } else {
         const int C = 2 * a.pairs;
         int32_t* e = a.env_i32 + (size_t)i * kRolloutEnvInts;
@@ -163,8 +174,17 @@ __global__ __launch_bounds__(DTQN_THREADS) void dtqn_rollout_step_kernel(Rollout
         }
         double reward;
         bool done, success;
-        if (a.kind == DTQN_ROLLOUT_CARFLAG) rollout_carflag_step(a.env_f64 + (size_t)i * 4, action, reward, done, success);
-        else rollout_memory_step(a.env_i32 + (size_t)i * kRolloutEnvInts, a.pairs, action, rollout_u(a.seed, a.vstep, i, kDrawCard), reward, done, success);
+        if (a.kind == DTQN_ROLLOUT_CARFLAG) {
+            rollout_carflag_step(a.env_f64 + (size_t)i * 4, action, reward, done, success);
+        } else if (a.kind == DTQN_ROLLOUT_POMDP) {
+            double* rec = a.env_f64 + (size_t)i * 4;                  // the draws, recorded: [0], [1] those of this step
+            const double u_state = rollout_u(a.seed, a.vstep, i, kDrawPomdpState), u_obs = rollout_u(a.seed, a.vstep, i, kDrawPomdpObs);
+            rollout_pomdp_step(a.env_i32 + (size_t)i * kRolloutEnvInts, a.pomdp, action, u_state, u_obs, reward, done, success);
+            rec[0] = u_state;
+            rec[1] = u_obs;
+        } else {
+            rollout_memory_step(a.env_i32 + (size_t)i * kRolloutEnvInts, a.pairs, action, rollout_u(a.seed, a.vstep, i, kDrawCard), reward, done, success);
+        }
         // gym TimeLimit (time_limit.py): the cap ends the episode; a truncated step is stored as not done (run.py:113)
         const int steps = t + 1;
         bool truncated = false;
@@ -174,6 +194,8 @@ __global__ __launch_bounds__(DTQN_THREADS) void dtqn_rollout_step_kernel(Rollout
         if (a.kind == DTQN_ROLLOUT_CARFLAG) {
             const double* s = a.env_f64 + (size_t)i * 4;
             for (int k = 0; k < 3; ++k) srow[k] = (float)s[k];        // f32 only where the observation is stored
+        } else if (a.kind == DTQN_ROLLOUT_POMDP) {
+            srow[0] = (float)a.env_i32[(size_t)i * kRolloutEnvInts + 1];
         } else {
             const int32_t* shown = a.env_i32 + (size_t)i * kRolloutEnvInts + 1 + 2 * a.pairs;
             for (int k = 0; k < O; ++k) srow[k] = (float)shown[k];
@@ -285,6 +307,8 @@ static RolloutArgs rollout_args(const DtqnNet* net, const DtqnReplay* rp, const 
     a.kind = ro->env_kind; a.n_envs = ro->n_envs; a.cap = ro->max_episode_steps; a.pairs = ro->num_pairs; a.pos0 = ro->pos0;
     a.L = net->ctx_len; a.O = net->obs_dim; a.A = net->num_actions;
     a.seed = ro->seed; a.vstep = vstep;
+    if (ro->env_kind == DTQN_ROLLOUT_POMDP)
+        a.pomdp = pomdp_tables(ro->pomdp_tables, ro->pomdp_states, ro->pomdp_actions, ro->pomdp_obs, ro->pomdp_first_obs_action);
     return a;
 }
 
@@ -299,6 +323,9 @@ int rollout_check(const DtqnNet* net, const DtqnReplay* rp, const DtqnRollout* r
     } else if (ro->env_kind == DTQN_ROLLOUT_MEMORY) {
         if (ro->num_pairs < 1 || 1 + 4 * ro->num_pairs > kRolloutEnvInts) return DTQN_ERR_ARG;
         if (net->obs_dim != 2 * ro->num_pairs || net->num_actions != 2 * ro->num_pairs) return DTQN_ERR_ARG;
+    } else if (ro->env_kind == DTQN_ROLLOUT_POMDP) {
+        if (pomdp_check(net, ro->pomdp_tables, ro->pomdp_states, ro->pomdp_obs, ro->pomdp_first_obs_action) != DTQN_OK) return DTQN_ERR_ARG;
+        if (net->num_actions != ro->pomdp_actions) return DTQN_ERR_ARG;
     } else {
         return DTQN_ERR_ARG;
     }
@@ -343,6 +370,14 @@ extern "C" long long dtqn_rollout_state_bytes(const DtqnNet* net, const DtqnRepl
     if (l.bytes > 0x7fffffffull) return -1;
     if (offsets != nullptr)
         for (int k = 0; k < DTQN_ROLLOUT_OFFSETS; ++k) offsets[k] = (int32_t)l.off[k];
+    return (long long)l.bytes;
+}
+
+extern "C" long long dtqn_pomdp_table_bytes(int states, int actions, int observations, long long* offsets) {
+    if (states < 1 || actions < 1 || observations < 1) return -1;
+    const PomdpLayout l = pomdp_layout(states, actions, observations);
+    if (offsets != nullptr)
+        for (int k = 0; k < DTQN_POMDP_SECTIONS; ++k) offsets[k] = (long long)l.off[k];
     return (long long)l.bytes;
 }
 

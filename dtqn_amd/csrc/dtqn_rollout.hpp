@@ -112,6 +112,88 @@ __device__ __forceinline__ void rollout_memory_step(int32_t* e, int pairs, int a
     }
 }
 
+// ---- tabular POMDP (DTQN_ROLLOUT_POMDP): three dense tables and two inverse-CDF draws per step ---------------------------------------
+// Byte offsets of the sections of the packed table buffer (DtqnRollout::pomdp_tables, DtqnEval::pomdp_tables), every section 16-byte
+// aligned: start_cdf f64[S] | T_cdf f64[A][S][S] | O_cdf f64[A][S][Z] | R f64[A][S][S][Z] | D u8[A][S].  The CDFs are derived once
+// on the host (envs/pomdp_file.py): every entry from the last positive probability onward is exactly 1.0.
+struct PomdpLayout {
+    size_t off[DTQN_POMDP_SECTIONS];
+    size_t bytes;
+};
+inline PomdpLayout pomdp_layout(int states, int actions, int observations) {
+    PomdpLayout l;
+    const size_t S = (size_t)states, A = (size_t)actions, Z = (size_t)observations;
+    const size_t sizes[DTQN_POMDP_SECTIONS] = {8 * S, 8 * A * S * S, 8 * A * S * Z, 8 * A * S * S * Z, A * S};
+    size_t at = 0;
+    for (int k = 0; k < DTQN_POMDP_SECTIONS; ++k) {
+        l.off[k] = at;
+        at += (sizes[k] + 15) & ~(size_t)15;
+    }
+    l.bytes = at;
+    return l;
+}
+
+struct PomdpTables {
+    const double *start_cdf, *t_cdf, *o_cdf, *r;
+    const uint8_t* d;
+    int S, A, Z, first_obs_action;
+};
+inline PomdpTables pomdp_tables(const void* packed, int states, int actions, int observations, int first_obs_action) {
+    const PomdpLayout l = pomdp_layout(states, actions, observations);
+    const uint8_t* base = static_cast<const uint8_t*>(packed);
+    PomdpTables t;
+    t.start_cdf = reinterpret_cast<const double*>(base + l.off[0]);
+    t.t_cdf = reinterpret_cast<const double*>(base + l.off[1]);
+    t.o_cdf = reinterpret_cast<const double*>(base + l.off[2]);
+    t.r = reinterpret_cast<const double*>(base + l.off[3]);
+    t.d = base + l.off[4];
+    t.S = states; t.A = actions; t.Z = observations; t.first_obs_action = first_obs_action;
+    return t;
+}
+// DTQN_OK when the table fields of a descriptor fit the network: one token per observation, the table's action count, a first-observation
+// action inside it.
+inline int pomdp_check(const DtqnNet* net, const void* packed, int states, int observations, int first_obs_action) {
+    if (packed == nullptr || states < 1 || observations < 1) return DTQN_ERR_ARG;
+    if (net->obs_dim != 1 || net->num_actions < 1 || first_obs_action < 0 || first_obs_action >= net->num_actions) return DTQN_ERR_ARG;
+    return DTQN_OK;
+}
+
+// The first k with u < cdf[k]: an upper bound with the comparison of np.searchsorted(cdf, u, side="right"), clamped to the row (the
+// row ends in exactly 1.0 and u < 1, so the clamp never acts on a table built by the parser).  ceil(log2(n + 1)) dependent loads.
+__device__ __forceinline__ int rollout_pomdp_draw(const double* cdf, int n, double u) {
+    int lo = 0, len = n;
+    while (len > 0) {
+        const int half = len >> 1;
+        const bool right = !(u < cdf[lo + half]);
+        lo = right ? lo + half + 1 : lo;
+        len = right ? len - half - 1 : half;
+    }
+    return lo < n ? lo : n - 1;
+}
+
+// TabularPOMDP.reset_with (envs/pomdp.py): s0 from `start`, the first observation from O[first_obs_action][s0].  e: state | observation.
+__device__ __forceinline__ void rollout_pomdp_reset(int32_t* e, const PomdpTables& t, double u_state, double u_obs) {
+    const int s0 = rollout_pomdp_draw(t.start_cdf, t.S, u_state);
+    e[0] = s0;
+    e[1] = rollout_pomdp_draw(t.o_cdf + ((size_t)t.first_obs_action * t.S + s0) * t.Z, t.Z, u_obs);
+}
+
+// TabularPOMDP.step_with: s' from T[a][s], z from O[a][s'], reward R[a][s][s'][z], done D[a][s].  (A state or an action from outside
+// -- set_state, a forced action -- is clamped into the tables.)
+__device__ __forceinline__ void rollout_pomdp_step(int32_t* e, const PomdpTables& t, int action, double u_state, double u_obs, double& reward,
+                                                   bool& done, bool& success) {
+    const int s = e[0] < 0 ? 0 : (e[0] < t.S ? e[0] : t.S - 1);
+    const int a = action < 0 ? 0 : (action < t.A ? action : t.A - 1);
+    const size_t row = (size_t)a * t.S + s;
+    const int s2 = rollout_pomdp_draw(t.t_cdf + row * t.S, t.S, u_state);
+    const int z = rollout_pomdp_draw(t.o_cdf + ((size_t)a * t.S + s2) * t.Z, t.Z, u_obs);
+    reward = t.r[(row * t.S + s2) * t.Z + z];
+    done = t.d[row] != 0;
+    success = done && reward > 0.0;
+    e[0] = s2;
+    e[1] = z;
+}
+
 // Byte offsets of the sections of DtqnRollout::state (include/dtqn_hip.h lists them), every section 16-byte aligned.
 struct RolloutLayout {
     size_t off[DTQN_ROLLOUT_OFFSETS];

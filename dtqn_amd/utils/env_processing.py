@@ -15,10 +15,11 @@ def _kind(space) -> str:
     return type(space).__name__
 
 
-def make_env(id_or_path: str):
-    """Registered id -> env.  (The reference falls back to a gridverse YAML factory here,
-    utils/env_processing.py:36-54; that simulator is not available, see dtqn_amd.envs.)"""
-    return _envs.make(id_or_path)
+def make_env(id_or_path: str, max_episode_steps=None):
+    """Registered id, POMDP id or `.pomdp` path -> env.  (The reference falls back to a gridverse YAML factory here,
+    utils/env_processing.py:36-54; that simulator is not available, see dtqn_amd.envs.)  max_episode_steps: the step cap of a
+    tabular POMDP (a `.pomdp` path needs one); the registered ids keep their own."""
+    return _envs.make(id_or_path, max_episode_steps=max_episode_steps)
 
 
 def is_discrete_env(env) -> bool:

@@ -389,14 +389,17 @@ int dtqn_actor_greedy_batch(const DtqnNet* net, const float* theta, const void* 
 int dtqn_debug_last_actor_live(void);
 
 /* ------------------------------------------------------------------------------------------
- * Device-resident rollout (dtqn_rollout.hip; DESIGN.md "Device-resident rollout"): N CarFlag or Memory environments, their rolling
+ * Device-resident rollout (dtqn_rollout.hip; DESIGN.md "Device-resident rollout"): N CarFlag, Memory or tabular POMDP environments, their rolling
  * contexts, the episodes in progress and the episode accounting live in ONE device allocation (`state`); a vector step is the
  * batched actor forward on the resident context block plus one one-workgroup kernel, with no host work in between.
  * state layout (byte offsets from dtqn_rollout_state_bytes; T = rp->max_steps, O = obs_dim, L = ctx_len, A = num_actions):
  *   [0] counters  i64[8]      episodes committed | env steps | successes | episodes finished | length sum | return sum (f64) |
  *                             episodes staged (finished with store != 0) | episodes dropped (pending ring full: the host broke its bound)
  *   [1] env_f64   f64[N][4]   CarFlag: position, velocity, direction, heaven position (+1 / -1)
+ *                             POMDP: the uniforms the kernel drew, recorded: u_state, u_obs of the last step | u_state, u_obs of the reset
+ *                             that started the episode in progress (a reset leaves the first two alone)
  *   [2] env_i32   i32[N][40]  Memory: current card | hidden values [cards] | shown table [cards]
+ *                             POMDP: state index | current observation
  *   [3] elapsed   i32[N]      steps of the episode in progress (= the context's timestep)
  *   [4] ep_ret    f64[N]      its return so far
  *   [5] last      i32[N][8]   last step: action | explored | done | stored done | truncated | success | episode reset | reward (f32 bits)
@@ -407,6 +410,12 @@ int dtqn_debug_last_actor_live(void);
  * ------------------------------------------------------------------------------------------ */
 #define DTQN_ROLLOUT_CARFLAG 0
 #define DTQN_ROLLOUT_MEMORY 1
+/* A tabular POMDP (envs/pomdp_file.py, DESIGN.md "Tabular POMDP environments"): S states, A actions, Z observations, one token per
+ * observation (obs_dim 1).  Its dynamics are one packed device buffer, every section 16-byte aligned (dtqn_pomdp_table_bytes):
+ *   start_cdf f64[S] | T_cdf f64[A][S][S] | O_cdf f64[A][S][Z] | R f64[A][S][S][Z] | D u8[A][S]
+ * A draw is the first k with u < cdf[k]; every CDF row ends in exactly 1.0 from its last positive probability onward. */
+#define DTQN_ROLLOUT_POMDP 2
+#define DTQN_POMDP_SECTIONS 5
 #define DTQN_ROLLOUT_OFFSETS 17
 #define DTQN_ROLLOUT_STATUS_WORDS 16
 typedef struct DtqnRollout {
@@ -416,14 +425,22 @@ typedef struct DtqnRollout {
     float* q_last;                    /* device [N][A]: Q of the last live row (whole-sequence networks write it) */
     float* q_dev;                     /* device [N][L][A] */
     float* workspace;                 /* as dtqn_actor_forward_batch for N */
-    int32_t env_kind;                 /* DTQN_ROLLOUT_CARFLAG / DTQN_ROLLOUT_MEMORY */
+    int32_t env_kind;                 /* DTQN_ROLLOUT_CARFLAG / DTQN_ROLLOUT_MEMORY / DTQN_ROLLOUT_POMDP */
     int32_t n_envs;
     int32_t max_episode_steps;        /* gym TimeLimit cap, <= rp->max_steps */
     int32_t num_pairs;                /* Memory: pairs on the table (1..8) */
     int32_t pos0;                     /* the k-th episode finished since attach goes to replay slot (pos0 + k) mod E */
     int32_t pending_slots;            /* K: finished episodes that may wait for the host's go-ahead (>= those of the vector steps the host runs ahead) */
     uint32_t seed;
+    const void* pomdp_tables;         /* POMDP: device, the packed tables (dtqn_pomdp_table_bytes); other kinds: unused */
+    int32_t pomdp_states;             /* S */
+    int32_t pomdp_actions;            /* A of the tables: must equal the network's num_actions */
+    int32_t pomdp_obs;                /* Z */
+    int32_t pomdp_first_obs_action;   /* the action whose O row gives the observation of a reset (< A) */
 } DtqnRollout;
+/* Bytes of the packed POMDP tables; offsets (may be NULL): i64[DTQN_POMDP_SECTIONS] byte offsets of start_cdf, T_cdf, O_cdf, R, D.
+ * < 0: bad arguments. */
+long long dtqn_pomdp_table_bytes(int states, int actions, int observations, long long* offsets);
 /* Bytes of `state`; offsets (may be NULL): int32[DTQN_ROLLOUT_OFFSETS] byte offsets of the sections above.  < 0: bad arguments. */
 long long dtqn_rollout_state_bytes(const DtqnNet* net, const DtqnReplay* rp, const DtqnRollout* ro, int32_t* offsets);
 /* Reset every environment and start fresh contexts in block 0 (draws keyed by (seed, vstep, env)); counters are kept. */
@@ -445,14 +462,14 @@ int dtqn_rollout_get_state(const DtqnNet* net, const DtqnReplay* rp, const DtqnR
 int dtqn_rollout_set_state(const DtqnNet* net, const DtqnReplay* rp, const DtqnRollout* ro, const void* host, void* stream);
 /* ------------------------------------------------------------------------------------------
  * Device-resident greedy evaluation (dtqn_deval.hip; DESIGN.md "Device-resident evaluation"): a quota of `episodes` greedy episodes
- * played by N CarFlag or Memory environments in ONE device allocation (`state`).  Environment i plays episodes i, i + N, ...; with
+ * played by N CarFlag, Memory or tabular POMDP environments in ONE device allocation (`state`).  Environment i plays episodes i, i + N, ...; with
  * none left it goes idle (len = 1, no step, never counted).  Every draw of an episode is a function of (seed, key, episode index,
  * step within the episode, draw kind): the same episode whatever N plays it.
  * state layout (byte offsets from dtqn_deval_state_bytes; O = obs_dim, L = ctx_len, A = num_actions, K = max_episodes):
  *   [0] counters  i64[8]      episodes finished | env steps | successes | length sum | return sum (f64) | environments still playing |
  *                             vector steps of this evaluation | 0
- *   [1] env_f64   f64[N][4]   CarFlag: position, velocity, direction, heaven position (+1 / -1)
- *   [2] env_i32   i32[N][40]  Memory: current card | hidden values [cards] | shown table [cards]
+ *   [1] env_f64   f64[N][4]   CarFlag: position, velocity, direction, heaven position (+1 / -1); POMDP: the recorded uniforms, as the rollout's
+ *   [2] env_i32   i32[N][40]  Memory: current card | hidden values [cards] | shown table [cards]; POMDP: state index | current observation
  *   [3] elapsed   i32[N]      steps of the episode in progress (= the context's timestep)
  *   [4] ep_ret    f64[N]      its return so far
  *   [5] episode   i32[N]      index of the episode in progress, -1 = idle
@@ -472,12 +489,17 @@ typedef struct DtqnEval {
     float* q_last;                    /* device [N][A]: Q of the last live row (whole-sequence networks write it) */
     float* q_dev;                     /* device [N][L][A] */
     float* workspace;                 /* as dtqn_actor_forward_batch for N */
-    int32_t env_kind;                 /* DTQN_ROLLOUT_CARFLAG / DTQN_ROLLOUT_MEMORY */
+    int32_t env_kind;                 /* DTQN_ROLLOUT_CARFLAG / DTQN_ROLLOUT_MEMORY / DTQN_ROLLOUT_POMDP */
     int32_t n_envs;
     int32_t max_episode_steps;        /* gym TimeLimit cap */
     int32_t num_pairs;                /* Memory: pairs on the table (1..8) */
     int32_t max_episodes;             /* K: rows of the results table */
     uint32_t seed;
+    const void* pomdp_tables;         /* POMDP: the packed tables and their sizes, as DtqnRollout's */
+    int32_t pomdp_states;
+    int32_t pomdp_actions;
+    int32_t pomdp_obs;
+    int32_t pomdp_first_obs_action;
 } DtqnEval;
 /* Bytes of `state`; offsets (may be NULL): int32[DTQN_DEVAL_OFFSETS] byte offsets of the sections above.  < 0: bad arguments. */
 long long dtqn_deval_state_bytes(const DtqnNet* net, const DtqnEval* ev, int32_t* offsets);

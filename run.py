@@ -36,7 +36,9 @@ def get_args(argv: Optional[Sequence[str]] = None):
     p.add_argument("--time-limit", type=float, default=None, help="hours before checkpointing and exiting")
     p.add_argument("--model", type=str, default="DTQN", choices=list(MODEL_MAP.keys()))
     p.add_argument("--envs", type=str, nargs="+", default=["DiscreteCarFlag-v0"],
-                   help="one or more domains with identical observation / action spaces")
+                   help="one or more domains with identical observation / action spaces; tabular POMDPs: POMDP-<name>-episodic-v0, "
+                        "POMDP-<name>-v0 (<name>.pomdp from DTQN_POMDP_PATH or the bundled tiger / corridor) or a path ending in .pomdp "
+                        "(needs --max-episode-steps)")
     p.add_argument("--num-steps", type=int, default=2_000_000, help="environment steps to train for")
     p.add_argument("--tuf", type=int, default=10_000, help="hard target-update period (in updates)")
     p.add_argument("--lr", type=float, default=3e-4)
@@ -73,8 +75,8 @@ def get_args(argv: Optional[Sequence[str]] = None):
                         "batched actor launch and keeps the reference's 1 env step : 1 update ratio by running N updates per "
                         "vector step (all N actions of a vector step come from the same parameters)")
     p.add_argument("--device-envs", type=int, default=0,
-                   help="device-resident rollout (dtqn_amd.agents.device_rollout.DeviceVectorActor): N > 0 steps N CarFlag / Memory "
-                        "environments on the GPU behind the batched actor forward, prepopulation included; the loop is that of "
+                   help="device-resident rollout (dtqn_amd.agents.device_rollout.DeviceVectorActor): N > 0 steps N CarFlag / Memory / "
+                        "tabular POMDP environments on the GPU behind the batched actor forward, prepopulation included; the loop is that of "
                         "--num-envs (N updates per vector step).  Needs --sampler device; 0 = off")
     p.add_argument("--overlap", action="store_true",
                    help="pipeline the actor forward of step t+1 with TD update t+1 on two HIP streams (same policy-vs-action "
@@ -84,7 +86,7 @@ def get_args(argv: Optional[Sequence[str]] = None):
                         "launch per step (dtqn_amd.agents.vector.VectorEvaluator); 1 evaluates through the single-environment actor")
     p.add_argument("--device-eval-envs", type=int, default=0,
                    help="device-resident greedy evaluation (dtqn_amd.agents.device_eval.DeviceEvaluator): N > 0 plays the evaluation "
-                        "episodes of CarFlag / Memory domains N at a time on the GPU, with no host round trip per step; with or without "
+                        "episodes of CarFlag / Memory / tabular POMDP domains N at a time on the GPU, with no host round trip per step; with or without "
                         "--device-envs, not with --eval-envs > 1; 0 = off")
     return p.parse_args(argv)
 
@@ -241,8 +243,9 @@ def run_experiment(args):
             raise ValueError("--device-eval-envs and --eval-envs > 1 exclude each other: the evaluation environments live on the device or on the host")
         if world > 1:
             raise NotImplementedError("--device-eval-envs: data-parallel runs are not covered")
-    envs = [env_processing.make_env(e) for e in args.envs]
-    eval_envs = [env_processing.make_env(e) for e in args.envs]
+    cap = args.max_episode_steps if args.max_episode_steps > 0 else None     # tabular POMDPs: their step cap (a .pomdp path needs one)
+    envs = [env_processing.make_env(e, cap) for e in args.envs]
+    eval_envs = [env_processing.make_env(e, cap) for e in args.envs]
     set_global_seed(args.seed + rank, *(envs + eval_envs))         # per-rank env / replay / exploration streams
     eps = epsilon_anneal.LinearAnneal(1.0, 0.1, args.num_steps // 10)
     agent = get_agent(args.model, envs, args.obs_embed, args.a_embed, args.in_embed, args.buf_size, device, args.lr,
@@ -252,11 +255,13 @@ def run_experiment(args):
     if is_main:
         print(f"[ {timestamp()} ] Creating {args.model} with "
               f"{sum(p.numel() for p in agent.policy_network.parameters())} parameters", flush=True)
-    save_dir = os.path.join(os.getcwd(), "policies", args.project_name, *args.envs)
+    # names for directories and files: a .pomdp path goes by its file name
+    env_tags = [os.path.splitext(os.path.basename(e))[0] if e.endswith(".pomdp") else e for e in args.envs]
+    save_dir = os.path.join(os.getcwd(), "policies", args.project_name, *env_tags)
     os.makedirs(save_dir, exist_ok=True)
     policy_path = os.path.join(
         save_dir,
-        f"model={args.model}_envs={','.join(args.envs)}_obs_embed={args.obs_embed}_a_embed={args.a_embed}_"
+        f"model={args.model}_envs={','.join(env_tags)}_obs_embed={args.obs_embed}_a_embed={args.a_embed}_"
         f"in_embed={args.in_embed}_context={args.context}_heads={args.heads}_layers={args.layers}_batch={args.batch}_"
         f"gate={args.gate}_identity={args.identity}_history={args.history}_pos={args.pos}_bag={args.bag_size}_seed={args.seed}")
     if args.render:
@@ -304,7 +309,7 @@ def run_experiment(args):
     if args.num_envs > 1:
         from dtqn_amd.agents.vector import VectorActor
         # N copies of the (first) training domain, each with its own seed
-        venvs = [env_processing.make_env(args.envs[k % len(args.envs)]) for k in range(args.num_envs)]
+        venvs = [env_processing.make_env(args.envs[k % len(args.envs)], cap) for k in range(args.num_envs)]
         for k, e in enumerate(venvs):
             e.seed(args.seed + 1000 * (rank + 1) + k)
         vector = VectorActor(agent, venvs, ref_quirks=args.ref_quirks)
@@ -314,7 +319,7 @@ def run_experiment(args):
         # N copies of every evaluation domain, seeded like the --num-envs copies (in a range of their own)
         evaluators = []
         for d, env_str in enumerate(args.envs):
-            copies = [env_processing.make_env(env_str) for _ in range(args.eval_envs)]
+            copies = [env_processing.make_env(env_str, cap) for _ in range(args.eval_envs)]
             for k, e in enumerate(copies):
                 e.seed(args.seed + 1000 * (rank + 1) + 500 + d * args.eval_envs + k)
             evaluators.append(VectorEvaluator(agent, copies, ref_quirks=args.ref_quirks))
