@@ -73,7 +73,6 @@ __device__ __forceinline__ float direct_tile(const DtqnNet& net, const DirectCtx
     float bsum = 0.f;
     const int nsub = LP / 16;                                         // 16-token units per sequence
     const int per_layer = a.batch * nsub, units = per_layer * job.n_layers;
-    const int mine = (units - t.wave + WV - 1) / WV;   // units w, w + 8, ... of this wave
     // groups of kDGroup units a wave can get (B * LP * layers <= kDirectMaxTokens): with one, the second buffer and the loop fold away
     constexpr int kMaxGroups = (kDirectMaxTokens / 16 + WV * kDGroup - 1) / (WV * kDGroup);
     constexpr int NBUF = kMaxGroups > 1 ? 2 : 1;
@@ -86,72 +85,96 @@ __device__ __forceinline__ float direct_tile(const DtqnNet& net, const DirectCtx
     // units w, w + 8, ... of this wave, walked incrementally as (layer, sequence, 16-token block): no divisions in
     // front of the loads; all of it is wave-uniform (scalar registers)
     const int wv = __builtin_amdgcn_readfirstlane(t.wave);
+    const int mine = (units - wv + WV - 1) / WV;       // units w, w + WV, ... of this wave
     int u_lyr = 0, u_sq = wv / nsub, u_sub = wv - u_sq * nsub, u_m = 0;
     while (u_sq >= a.batch) { u_sq -= a.batch; ++u_lyr; }
     const int inc_sq = WV / nsub, inc_sub = WV - inc_sq * nsub;
     const size_t ylane = (size_t)job.dy_off + (size_t)t.kq * job.ldy + ycol_c;       // float index into grd
     const float* xlane = xbase + (size_t)t.kq * job.ldx + xcol_c;
-    auto group_load = [&](float (&a4)[kDGroup][4], float2 (&b4)[kDGroup][4]) {
-#pragma unroll
-        for (int q = 0; q < kDGroup; ++q) {
-            const bool live = u_m < mine;                             // past the end: re-read unit (0, 0, 0), zeroed in group_mma
-            const int lyr = live ? u_lyr : 0, sq = live ? u_sq : 0, sub = live ? u_sub : 0;
-            const size_t yp = ylane + (size_t)sq * ystride + (size_t)lyr * job.dy_lstride + (size_t)(sub * 16) * job.ldy;
-            const float* xp = xlane + (size_t)sq * xstride + (size_t)lyr * job.x_lstride + (size_t)(sub * 16) * job.ldx;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                a4[q][k] = direct_ld<SC1>(a.grd, grs, yp + (size_t)4 * k * job.ldy);
-                b4[q][k] = *reinterpret_cast<const float2*>(xp + (size_t)4 * k * job.ldx);
-            }
-            ++u_m;
-            u_sub += inc_sub; u_sq += inc_sq;
-            if (u_sub >= nsub) { u_sub -= nsub; ++u_sq; }
-            while (u_sq >= a.batch) { u_sq -= a.batch; ++u_lyr; }
-        }
-    };
-    auto group_mma = [&](int g, const float (&a4)[kDGroup][4], const float2 (&b4)[kDGroup][4]) {
-#pragma unroll
-        for (int q = 0; q < kDGroup; ++q) {
-            const float keep = (yok && g * kDGroup + q < mine) ? 1.f : 0.f;     // zero A: the product and the bias sum vanish
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float av_ = keep != 0.f ? a4[q][k] : 0.f;
-                bsum += av_;
-                acc[0] = mfma16(av_, b4[q][k].x, acc[0]);
-                acc[1] = mfma16(av_, b4[q][k].y, acc[1]);
-            }
-        }
-    };
+    // Rows at or past the context hold an all-zero dY (the backward leaves it there): their 4-token steps add exact zeros.  A wave's units
+    // advance by WV; where that is a multiple of the units per sequence (inc_sub == 0: 16 or 8 waves on 1, 2 or 4 units per sequence)
+    // EVERY unit of a wave has the same place u_sub in its sequence, so the number of steps that hold a live row is one scalar per wave
+    // and tile (context 50 in 64-row records: waves 3, 7, 11, 15 own the fourth units, one live step each, the other twelve only full
+    // units).  One wave-uniform branch in front of the walk picks a body compiled for that many steps per unit; inside a body nothing
+    // is conditional.  Bag networks contract every row; units that change their place (inc_sub != 0) keep the four steps.
+    int steps = 4;
+    if (inc_sub == 0) {
+        const int live_rows = net.bag_size > 0 ? LP : net.ctx_len, left = live_rows - 16 * u_sub;
+        steps = left >= 16 ? 4 : left <= 0 ? 0 : (left + 3) / 4;
+    }
+    steps = __builtin_amdgcn_readfirstlane(steps);
     const int ngroups = (mine + kDGroup - 1) / kDGroup;
-    if constexpr (kMaxGroups == 1) {
-        group_load(av[0], bv[0]);
-        DTQN_SCHED_FENCE();
-        DTQN_PROF_CLOCK(clk.loads);
-        group_mma(0, av[0], bv[0]);
-    } else {
-        constexpr int B1 = NBUF - 1;
-        if (ngroups > 0) group_load(av[0], bv[0]);
-        DTQN_SCHED_FENCE();
-        int g = 0;
-        for (; g + 2 < ngroups; g += 2) {                                 // buffers alternate without dynamic indexing
-            group_load(av[B1], bv[B1]);
-            DTQN_SCHED_FENCE();
-            group_mma(g, av[0], bv[0]);
-            DTQN_SCHED_FENCE();
+    // the walk over this wave's units at STEPS 4-token steps per unit (a std::integral_constant: the loops' bound at compile time)
+    auto walk = [&](auto steps_c) {
+        constexpr int STEPS = decltype(steps_c)::value;
+        auto group_load = [&](float (&a4)[kDGroup][4], float2 (&b4)[kDGroup][4]) {
+#pragma unroll
+            for (int q = 0; q < kDGroup; ++q) {
+                const bool live = u_m < mine;                         // past the end: re-read unit (0, 0, 0), zeroed in group_mma
+                const int lyr = live ? u_lyr : 0, sq = live ? u_sq : 0, sub = live ? u_sub : 0;
+                const size_t yp = ylane + (size_t)sq * ystride + (size_t)lyr * job.dy_lstride + (size_t)(sub * 16) * job.ldy;
+                const float* xp = xlane + (size_t)sq * xstride + (size_t)lyr * job.x_lstride + (size_t)(sub * 16) * job.ldx;
+#pragma unroll
+                for (int k = 0; k < STEPS; ++k) {
+                    a4[q][k] = direct_ld<SC1>(a.grd, grs, yp + (size_t)4 * k * job.ldy);
+                    b4[q][k] = *reinterpret_cast<const float2*>(xp + (size_t)4 * k * job.ldx);
+                }
+                ++u_m;
+                u_sub += inc_sub; u_sq += inc_sq;
+                if (u_sub >= nsub) { u_sub -= nsub; ++u_sq; }
+                while (u_sq >= a.batch) { u_sq -= a.batch; ++u_lyr; }
+            }
+        };
+        auto group_mma = [&](int g, const float (&a4)[kDGroup][4], const float2 (&b4)[kDGroup][4]) {
+#pragma unroll
+            for (int q = 0; q < kDGroup; ++q) {
+                const float keep = (yok && g * kDGroup + q < mine) ? 1.f : 0.f;     // zero A: the product and the bias sum vanish
+#pragma unroll
+                for (int k = 0; k < STEPS; ++k) {
+                    const float av_ = keep != 0.f ? a4[q][k] : 0.f;
+                    bsum += av_;
+                    acc[0] = mfma16(av_, b4[q][k].x, acc[0]);
+                    acc[1] = mfma16(av_, b4[q][k].y, acc[1]);
+                }
+            }
+        };
+        if constexpr (kMaxGroups == 1) {
             group_load(av[0], bv[0]);
             DTQN_SCHED_FENCE();
-            group_mma(g + 1, av[B1], bv[B1]);
+            DTQN_PROF_CLOCK(clk.loads);
+            group_mma(0, av[0], bv[0]);
+        } else {
+            constexpr int B1 = NBUF - 1;
+            if (ngroups > 0) group_load(av[0], bv[0]);
             DTQN_SCHED_FENCE();
+            int g = 0;
+            for (; g + 2 < ngroups; g += 2) {                             // buffers alternate without dynamic indexing
+                group_load(av[B1], bv[B1]);
+                DTQN_SCHED_FENCE();
+                group_mma(g, av[0], bv[0]);
+                DTQN_SCHED_FENCE();
+                group_load(av[0], bv[0]);
+                DTQN_SCHED_FENCE();
+                group_mma(g + 1, av[B1], bv[B1]);
+                DTQN_SCHED_FENCE();
+            }
+            if (g + 1 < ngroups) {                                        // last pair (cfg 1: the only one -- all 16 units in flight at once)
+                group_load(av[B1], bv[B1]);
+                DTQN_SCHED_FENCE();
+                group_mma(g, av[0], bv[0]);
+                DTQN_SCHED_FENCE();
+                group_mma(g + 1, av[B1], bv[B1]);
+            } else if (g < ngroups) {
+                group_mma(g, av[0], bv[0]);
+            }
         }
-        if (g + 1 < ngroups) {                                            // last pair (cfg 1: the only one -- all 16 units in flight at once)
-            group_load(av[B1], bv[B1]);
-            DTQN_SCHED_FENCE();
-            group_mma(g, av[0], bv[0]);
-            DTQN_SCHED_FENCE();
-            group_mma(g + 1, av[B1], bv[B1]);
-        } else if (g < ngroups) {
-            group_mma(g, av[0], bv[0]);
-        }
+    };
+    switch (steps) {
+        case 4: walk(std::integral_constant<int, 4>{}); break;
+        case 3: walk(std::integral_constant<int, 3>{}); break;
+        case 2: walk(std::integral_constant<int, 2>{}); break;
+        case 1: walk(std::integral_constant<int, 1>{}); break;
+        default: DTQN_PROF_CLOCK(clk.loads); break;                       // no live row in any unit of this wave (context 33 .. 48 in 64-row records)
     }
 #ifdef DTQN_ENABLE_PROF
     asm volatile("" : "+v"(acc[0]), "+v"(acc[1]));                      // the last MFMA has delivered
@@ -161,12 +184,17 @@ __device__ __forceinline__ float direct_tile(const DtqnNet& net, const DirectCtx
     bsum += __shfl_xor(bsum, 16);
     bsum += __shfl_xor(bsum, 32);
     // cross-wave sum through LDS, fixed order: slab[n][k] (+ a bias row) per wave
+    // (the lane's place in the tile is derived again from the thread index: held in registers across the walk, kq and i would be
+    // two more beside the 104 of operands and sums)
     constexpr int SLD = kDTK + 4;
-    float* slab = slabs + (size_t)t.wave * (kDTN + 1) * SLD;
+    int tid_e = tid;
+    DTQN_ASM_KEEP(tid_e);
+    const int kq_e = (tid_e >> 4) & 3, i_e = tid_e & 15;
+    float* slab = slabs + (size_t)wv * (kDTN + 1) * SLD;
 #pragma unroll
     for (int r = 0; r < 4; ++r)
-        *reinterpret_cast<float2*>(slab + (t.kq * 4 + r) * SLD + 2 * t.i) = make_float2(acc[0][r], acc[1][r]);
-    if (t.kq == 0) slab[kDTN * SLD + t.i] = bsum;
+        *reinterpret_cast<float2*>(slab + (kq_e * 4 + r) * SLD + 2 * i_e) = make_float2(acc[0][r], acc[1][r]);
+    if (kq_e == 0) slab[kDTN * SLD + i_e] = bsum;
     __syncthreads();
     if (tid < kDTN * (kDTK / 4)) {
         const int nl = tid / (kDTK / 4), k4 = (tid % (kDTK / 4)) * 4;
@@ -269,10 +297,12 @@ __device__ __forceinline__ float direct_small(const DtqnNet& net, const DirectCt
 template <int WV>
 __device__ __forceinline__ void direct_norm_partial(float ss, float* red, float* norm_partial, int slot, const Thr& t) {
     ss = wave_sum(ss);
+    int tid_e = t.tid;                       // lane and wave derived again behind the tile: two registers less across direct_tile's walk
+    DTQN_ASM_KEEP(tid_e);
     __syncthreads();
-    if (t.lane == 0) red[t.wave] = ss;
+    if ((tid_e & 63) == 0) red[tid_e >> 6] = ss;
     __syncthreads();
-    if (t.tid == 0) {
+    if (tid_e == 0) {
         float tot = 0.f;
         for (int w = 0; w < WV; ++w) tot += red[w];
         norm_partial[slot] = tot;
