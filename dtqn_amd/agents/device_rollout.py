@@ -23,7 +23,6 @@ when it has its steps (the host loop finishes its last episode); `step_all` does
 """
 from __future__ import annotations
 
-import ctypes
 from types import SimpleNamespace
 from typing import Optional
 
@@ -31,120 +30,45 @@ import numpy as np
 import torch
 
 from .. import _binding as B
-from .. import dist as ddp
-from .. import envs as _envs
+from .device_env import ENV_KINDS, DeviceEnvs, make_device_env, upload_pomdp_tables  # noqa: F401  (re-exported: run.py, tests, tests/perf)
 
-ENV_KINDS = {"DiscreteCarFlag-v0": B.DEFINES["DTQN_ROLLOUT_CARFLAG"], "Memory-5-v0": B.DEFINES["DTQN_ROLLOUT_MEMORY"]}
 COUNTERS = ("committed", "env_steps", "successes", "finished", "length_sum", "return_sum", "staged", "dropped")
-_STATUS_WORDS, _OFFSETS = B.DEFINES["DTQN_ROLLOUT_STATUS_WORDS"], B.DEFINES["DTQN_ROLLOUT_OFFSETS"]
-_ENV_INTS, _LAST_INTS = 40, 8
 LAST_FIELDS = ("action", "explored", "done", "stored_done", "truncated", "success", "reset")
 
-_ptr = lambda t: ctypes.c_void_p(t.data_ptr())
 
-
-def make_device_env(env_id: str, max_episode_steps: Optional[int], what: str):
-    """The host twin of the device environments -> (env, kind).  A registered id names its kind; a tabular POMDP (an id or a `.pomdp`
-    path) is recognised from the made environment: a TabularPOMDP under the TimeLimit.  Anything else is refused."""
-    if env_id in ENV_KINDS:
-        return _envs.make(env_id), ENV_KINDS[env_id]
-    if _envs.is_pomdp(env_id):
-        env = _envs.make(env_id, max_episode_steps=max_episode_steps)
-        if isinstance(getattr(env, "env", None), _envs.TabularPOMDP):
-            return env, B.DEFINES["DTQN_ROLLOUT_POMDP"]
-    raise NotImplementedError(f"device-resident {what} covers {sorted(ENV_KINDS)} and tabular POMDPs, not {env_id!r}")
-
-
-def upload_pomdp_tables(lib, desc, env, device) -> torch.Tensor:
-    """Pack the model's tables (start_cdf | T_cdf | O_cdf | R | D) at the offsets the library states, upload them once and point the
-    descriptor (DtqnRollout / DtqnEval) at them -> the tensor, which the caller keeps alive."""
-    pomdp = env.env
-    S, A, Z = pomdp.model.sizes
-    offsets = (ctypes.c_longlong * B.DEFINES["DTQN_POMDP_SECTIONS"])()
-    nbytes = int(lib.dtqn_pomdp_table_bytes(S, A, Z, offsets))
-    if nbytes <= 0:
-        raise ValueError("dtqn_pomdp_table_bytes refused this model")
-    tables = torch.from_numpy(pomdp.model.pack(list(offsets), nbytes)).to(device)
-    desc.pomdp_tables = tables.data_ptr()
-    desc.pomdp_states, desc.pomdp_actions, desc.pomdp_obs, desc.pomdp_first_obs_action = S, A, Z, pomdp.first_obs_action
-    return tables
-
-
-class DeviceVectorActor:
-    RUN_AHEAD = 8                  # vector steps the host may be in front of the device; the pending ring is sized for them
+class DeviceVectorActor(DeviceEnvs):
+    WHAT, FLAG, COVERAGE = "rollout", "--num-envs", "network or replay"
+    ENTRY, DESC = "dtqn_rollout", B.DtqnRollout
+    COUNTERS, RETURN_SUM = COUNTERS, 5
+    LAST_SECTION, BLOCK_SECTION = 5, 6
 
     def __init__(self, agent, env_id: str, n_envs: int, seed: int, max_episode_steps: Optional[int] = None, num_pairs: Optional[int] = None):
-        env, kind = make_device_env(env_id, max_episode_steps, "rollout (use --num-envs otherwise)")
-        if getattr(agent, "image", None) is not None:
-            raise NotImplementedError("device-resident rollout: image networks are not covered (use --num-envs)")
-        if agent.bag.size > 0:
-            raise NotImplementedError("device-resident rollout: bag networks are not covered (use --num-envs)")
-        if agent.dp is not None or ddp.is_distributed():
-            raise NotImplementedError("device-resident rollout: data-parallel runs are not covered")
-        if agent.sampler != "device":
-            raise ValueError("device-resident rollout needs --sampler device: the host mirror of the episode lengths, which the reference "
-                             "sampler draws from, is only refreshed by sync()")
-        if n_envs < 1:
-            raise ValueError("device-resident rollout needs at least one environment")
-        self.agent, self.env_id, self.n, self.seed = agent, env_id, int(n_envs), int(seed) & 0xFFFFFFFF
-        eng, rb, dev = agent.engine, agent.replay_buffer, agent.device
-        self.L, self.O, self.A = agent.context_len, int(agent.env_obs_length), agent.num_actions
-        self.kind = kind
-        self.cap = int(max_episode_steps if max_episode_steps is not None else env._max_episode_steps)
-        self.pairs = int(num_pairs if num_pairs is not None else getattr(env, "num_pairs", 0))
+        super().__init__(agent, env_id, n_envs, seed, max_episode_steps, num_pairs)
+        rb = agent.replay_buffer
         if self.cap > rb.max_episode_steps:
             raise ValueError(f"the step cap {self.cap} exceeds the replay's {rb.max_episode_steps} rows per episode")
         rb.commit()                                      # nothing of a host producer may be left in the staging
         if rb.pos[1] != 0:
             raise ValueError("the replay has an episode in progress: flush() it before a device rollout attaches")
-        cuda = dev.type == "cuda"
-        pin = (lambda t: t.pin_memory()) if cuda else (lambda t: t)
-        N, L, A = self.n, self.L, self.A
-        self._forced = torch.full((N,), -1, dtype=torch.int32, device=dev)
-        self._q_last = torch.zeros(N * A, device=dev)
-        self._q_d = torch.zeros(N * L * A, device=dev)
-        need = eng.lib.dtqn_forward_workspace_floats(eng._actor_net_ref, N)
-        self._ws = torch.zeros(max(1, need), dtype=torch.float32, device=dev)
-        self._status_h = pin(torch.zeros(_STATUS_WORDS * 8, dtype=torch.uint8))
-        self._status_np = self._status_h.numpy().view(np.uint32).reshape(_STATUS_WORDS, 2)       # {word, tag} per granule
-        ro = self.ro = B.DtqnRollout()
-        ro.status_host, ro.forced_actions = self._status_h.data_ptr(), self._forced.data_ptr()
-        ro.q_last, ro.q_dev, ro.workspace = self._q_last.data_ptr(), self._q_d.data_ptr(), (self._ws.data_ptr() if need > 0 else None)
-        ro.env_kind, ro.n_envs, ro.max_episode_steps, ro.num_pairs = kind, N, self.cap, self.pairs
-        if kind == B.DEFINES["DTQN_ROLLOUT_POMDP"]:
-            self.env = env                               # the host twin: its model is what the device steps
-            self._tables = upload_pomdp_tables(eng.lib, ro, env, dev)
-        ro.pos0, ro.seed = int(rb.pos[0]), self.seed
-        ro.pending_slots = (self.RUN_AHEAD + 2) * N      # at most N episodes finish per vector step
-        self.pos0 = int(rb.pos[0])
-        self._ro_ref = ctypes.byref(ro)
-        offsets = (ctypes.c_int32 * _OFFSETS)()
-        nbytes = int(eng.lib.dtqn_rollout_state_bytes(eng._actor_net_ref, rb.dev.view_ref, self._ro_ref, offsets))
-        if nbytes <= 0:
-            raise ValueError("dtqn_rollout_state_bytes refused this shape")
-        self._offsets, self._nbytes = list(offsets), nbytes
-        self._state = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
-        self._state_h = pin(torch.zeros(nbytes, dtype=torch.uint8))
-        ro.state = self._state.data_ptr()
+        self._forced = torch.full((self.n,), -1, dtype=torch.int32, device=agent.device)
+        ro = self.ro = self._make_descriptor()
+        ro.forced_actions = self._forced.data_ptr()
+        ro.pos0 = self.pos0 = int(rb.pos[0])
+        ro.pending_slots = (self.RUN_AHEAD + 2) * self.n          # at most N episodes finish per vector step
+        self._ro_ref = self._desc_ref
+        self._alloc_state(ro)
         self._vstep = 0            # key of the next vector step's draws: never repeated
         self._since_reset = 0      # vector steps since reset_all: min(L, this + 1) bounds every live-row count
-        self._cur = 0              # the block that holds the contexts
         self.steps = 0             # env steps enqueued (the device's counter says how many have run)
-        self._seen = dict.fromkeys(COUNTERS, 0)
         self._authorized = 0       # episodes the launches so far were allowed to write into the replay
-        self._issued = 0           # vector steps enqueued
-        self._events = [torch.cuda.Event() for _ in range(self.RUN_AHEAD)] if cuda else None
-        self._check(eng.lib.dtqn_rollout_reset(eng._actor_net_ref, rb.dev.view_ref, self._ro_ref, 0, eng._stream()), "dtqn_rollout_reset")
-        # (the constructor's reset validates the descriptor against the network and the replay; reset_all repeats it for the caller)
+        self._call("reset", 0)     # (validates the descriptor against the network and the replay; reset_all repeats it for the caller)
+
+    def _refuse(self, agent) -> None:
+        if agent.sampler != "device":
+            raise ValueError("device-resident rollout needs --sampler device: the host mirror of the episode lengths, which the reference "
+                             "sampler draws from, is only refreshed by sync()")
 
     # ------------------------------------------------------------------------------------------
-    @staticmethod
-    def _check(rc: int, what: str) -> None:
-        if rc == B.DEFINES["DTQN_ERR_CONFIG"]:
-            raise NotImplementedError(f"{what}: this network or replay is outside the device-resident rollout's coverage")
-        if rc != 0:
-            raise RuntimeError(f"{what} failed with DTQN status {rc}")
-
     def _lib_args(self):
         eng = self.agent.engine
         return eng.lib, eng._actor_net_ref, self.agent.replay_buffer.dev.view_ref
@@ -161,8 +85,7 @@ class DeviceVectorActor:
 
     def reset_all(self) -> None:
         """Reset every environment and start fresh contexts; episodes in progress are dropped, counters kept."""
-        lib, net, rp = self._lib_args()
-        self._check(lib.dtqn_rollout_reset(net, rp, self._ro_ref, self._vstep & 0xFFFFFFFF, self.agent.engine._stream()), "dtqn_rollout_reset")
+        self._call("reset", self._vstep & 0xFFFFFFFF)
         self._vstep += 1           # (the reset's draws have a range of their own, but a repeated reset_all must not repeat them)
         self._since_reset, self._cur = 0, 0
 
@@ -170,14 +93,6 @@ class DeviceVectorActor:
         """Tests: actions[i] >= 0 overrides environment i's choice on the following steps (None / -1: not forced)."""
         a = np.full(self.n, -1, dtype=np.int32) if actions is None else np.asarray(actions, dtype=np.int32).reshape(self.n)
         self._forced.copy_(torch.from_numpy(a))
-
-    def _throttle(self) -> None:
-        """Never more than RUN_AHEAD vector steps in front of the device: the pending ring holds what can finish in that many."""
-        if self._events is None:
-            return                                   # (the emulation runs every launch to completion)
-        k = self._issued % len(self._events)
-        if self._issued >= len(self._events):
-            self._events[k].synchronize()            # the step issued RUN_AHEAD steps ago has run: its status record is in pinned memory
 
     def _authorize(self, staged: int) -> int:
         """The episodes a launch may write into the replay: those the host has SEEN finished.  It therefore knows which launch changes
@@ -204,29 +119,16 @@ class DeviceVectorActor:
                                    1 if store else 0, authorize, 1 if run_forward else 0, 1 if agent.train_mode.name == "TRAIN" else 0, seed,
                                    step & 0xFFFFFFFF, agent.engine._stream())
         self._check(rc, "dtqn_rollout_step")
-        if self._events is not None:
-            self._events[self._issued % len(self._events)].record(agent._main_stream)
-        self._issued += 1
+        self._issue()
         self._vstep += 1
         self._since_reset += 1
-        self._cur ^= 1
         self.steps += self.n
         for _ in range(updates):
             agent.train()
 
     def poll(self) -> dict:
         """The newest complete status record (no blocking) -> counters."""
-        snap = self._status_np.copy()
-        tags = snap[:, 1]
-        if tags[0] != 0 and (tags == tags[0]).all():          # every granule of one launch
-            words = snap[:, 0].astype(np.uint64)
-            vals = (words[0::2] | (words[1::2] << np.uint64(32))).astype(np.uint64)
-            ints = vals.view(np.int64)
-            got = {k: int(ints[j]) for j, k in enumerate(COUNTERS) if k != "return_sum"}
-            got["return_sum"] = float(vals[5:6].view(np.float64)[0])
-            if got["env_steps"] >= self._seen["env_steps"]:
-                self._seen = got
-        return dict(self._seen)
+        return self._poll("env_steps")
 
     def counters(self) -> dict:
         """Cumulative since construction: episodes committed to the replay, env steps, successes, episodes finished, the sums of their
@@ -237,18 +139,12 @@ class DeviceVectorActor:
     def sync(self) -> dict:
         """Drain the stream and write out the episodes that still wait in the pending ring; rb.pos and rb.episode_lengths then describe
         the device arrays exactly.  -> counters."""
-        agent, rb = self.agent, self.agent.replay_buffer
-        stream = agent._main_stream if agent.device.type == "cuda" else None
-        if stream is not None:
-            stream.synchronize()
+        rb = self.agent.replay_buffer
+        self._sync()
         got = self.poll()
         if got["staged"] > got["committed"]:
-            lib, net, rp = self._lib_args()
-            authorize = self._authorize(got["staged"])
-            self._check(lib.dtqn_rollout_commit(net, rp, self._ro_ref, (self._vstep - 1) & 0xFFFFFFFF, authorize, agent.engine._stream()),
-                        "dtqn_rollout_commit")
-            if stream is not None:
-                stream.synchronize()
+            self._call("commit", (self._vstep - 1) & 0xFFFFFFFF, self._authorize(got["staged"]))
+            self._sync()
             got = self.poll()
         if got["env_steps"] != self.steps or got["committed"] != got["staged"]:
             raise RuntimeError(f"device rollout: the status record reports {got}, {self.steps} env steps were enqueued")
@@ -268,55 +164,16 @@ class DeviceVectorActor:
         self.sync()
         self.reset_all()
 
-    # ---- state access (tests, sync) -----------------------------------------------------------------
+    # ---- state access (tests, sync): get_state / set_state / q_rows are DeviceEnvs' ------------------------------
     def _views(self, raw: np.ndarray) -> SimpleNamespace:
-        N, L, O, A, T = self.n, self.L, self.O, self.A, self.agent.replay_buffer.max_episode_steps
-        off = self._offsets
-        sec = lambda k, nbytes, dt: raw[off[k]:off[k] + nbytes].view(dt)
-        blocks = []
-        for k in (6, 7):
-            obs_b, act_b = N * L * O * 4, (N * L + 3) & ~3
-            base = off[k]
-            blocks.append(SimpleNamespace(obs=raw[base:base + obs_b].view(np.float32).reshape(N, L, O),
-                                          actions=raw[base + obs_b:base + obs_b + N * L].reshape(N, L),
-                                          lens=raw[base + obs_b + act_b:base + obs_b + act_b + 4 * N].view(np.int32)))
-        last = sec(5, 4 * N * _LAST_INTS, np.int32).reshape(N, _LAST_INTS)
-        return SimpleNamespace(
-            raw=raw, counters=sec(0, 64, np.int64), env_f64=sec(1, 32 * N, np.float64).reshape(N, 4),
-            env_i32=sec(2, 4 * N * _ENV_INTS, np.int32).reshape(N, _ENV_INTS), elapsed=sec(3, 4 * N, np.int32), ep_ret=sec(4, 8 * N, np.float64),
-            last=last, reward=last[:, 7].view(np.float32), blocks=blocks, block=blocks[self._cur],
-            stage_obs=sec(8, 4 * N * (T + 1) * O, np.float32).reshape(N, T + 1, O), stage_act=sec(9, N * T, np.uint8).reshape(N, T),
-            stage_rew=sec(10, 4 * N * T, np.float32).reshape(N, T), stage_done=sec(11, N * T, np.uint8).reshape(N, T))
+        N, O, T = self.n, self.O, self.agent.replay_buffer.max_episode_steps
+        return super()._views(
+            raw, stage_obs=self._section(raw, 8, 4 * N * (T + 1) * O, np.float32).reshape(N, T + 1, O),
+            stage_act=self._section(raw, 9, N * T, np.uint8).reshape(N, T), stage_rew=self._section(raw, 10, 4 * N * T, np.float32).reshape(N, T),
+            stage_done=self._section(raw, 11, N * T, np.uint8).reshape(N, T))
 
-    def get_state(self) -> SimpleNamespace:
-        """A host copy of the whole device state as named numpy views (include/dtqn_hip.h lists the sections); `block` is the context
-        block the next step reads.  Memory: env_i32[i] = current card | hidden values | shown table.  POMDP: env_i32[i] = state |
-        observation, env_f64[i] = the recorded uniforms (u_state, u_obs of the last step | of the reset that started the episode)."""
-        agent = self.agent
-        lib, net, rp = self._lib_args()
-        self._check(lib.dtqn_rollout_get_state(net, rp, self._ro_ref, _ptr(self._state_h), agent.engine._stream()), "dtqn_rollout_get_state")
-        if agent.device.type == "cuda":
-            agent._main_stream.synchronize()
-        return self._views(self._state_h.numpy().copy())
-
-    def set_state(self, state: SimpleNamespace) -> None:
-        """Write a state obtained from get_state (and edited in place) back to the device."""
-        agent = self.agent
-        lib, net, rp = self._lib_args()
-        self._state_h.numpy()[:] = state.raw
-        # n_max = min(L, steps since the reset + 1) must go on bounding every live-row count
+    def _note_state(self, state: SimpleNamespace) -> None:
         self._since_reset = max(self._since_reset, int(np.clip(state.elapsed, 0, self.cap).max()))
-        self._check(lib.dtqn_rollout_set_state(net, rp, self._ro_ref, _ptr(self._state_h), agent.engine._stream()), "dtqn_rollout_set_state")
-        if agent.device.type == "cuda":
-            agent._main_stream.synchronize()
 
-    def q_rows(self) -> np.ndarray:
-        """Tests: the Q rows the last step's actions were taken from, [N][A] (the lengths are those of the block that step read)."""
-        N, A = self.n, self.A
-        if not self.agent.engine.actor_net.tiled:
-            return self._q_last.cpu().numpy().reshape(N, A).copy()
-        st = self.get_state()
-        n_max = min(self.L, self._since_reset)              # the n_max of the step that ran last
-        lens = st.blocks[self._cur ^ 1].lens
-        q = self._q_d.cpu().numpy()[:N * n_max * A].reshape(N, n_max, A)
-        return np.stack([q[i, lens[i] - 1] for i in range(N)])
+    def _last_n_max(self) -> int:
+        return min(self.L, self._since_reset)

@@ -60,7 +60,7 @@ struct ActorGreedyArgs {
     int n_envs, n_max, A;
 };
 // One workgroup: thread t owns a contiguous range of environments, the live counts go through the scan, so environment i finds its
-// sequence without a map.  First maximum on ties, a NaN counts as the maximum (torch.argmax / np.argmax).
+// sequence without a map.  The action is first_argmax of the row (dtqn_actor.hpp).
 __global__ __launch_bounds__(AT) void actor_greedy_kernel(ActorGreedyArgs a) {
     __shared__ int32_t sums[AT];
     const int N = a.n_envs, A = a.A, per = (N + AT - 1) / AT;
@@ -75,18 +75,8 @@ __global__ __launch_bounds__(AT) void actor_greedy_kernel(ActorGreedyArgs a) {
             continue;
         }
         const float* row = a.q + ((size_t)j * a.n_max + (len - 1)) * A;
-        float best = row[0];
-        int arg = 0;
-        a.q_last[(size_t)i * A] = best;
-        for (int k = 1; k < A; ++k) {
-            const float v = row[k];
-            a.q_last[(size_t)i * A + k] = v;
-            if (v > best || (v != v && best == best)) {
-                best = v;
-                arg = k;
-            }
-        }
-        a.action[i] = arg;
+        for (int k = 0; k < A; ++k) a.q_last[(size_t)i * A + k] = row[k];
+        a.action[i] = first_argmax(row, A);
         ++j;
     }
 }

@@ -1,4 +1,4 @@
-// Host-side pieces the batched actor entry points share (dtqn_actor.hip, dtqn_image.hip, dtqn_api.cpp); no device code.
+// Host-side pieces the batched actor entry points share (dtqn_actor.hip, dtqn_image.hip, dtqn_api.cpp), and the one arg-max of a Q row.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -20,6 +20,21 @@ inline ActorBlock actor_block(const DtqnNet* net, const void* base, int n_envs) 
     uint8_t* p = static_cast<uint8_t*>(const_cast<void*>(base));
     return ActorBlock{reinterpret_cast<float*>(p), p + obs_bytes, reinterpret_cast<int32_t*>(p + obs_bytes + act_bytes),
                       obs_bytes + act_bytes + sizeof(int32_t) * (size_t)n_envs};
+}
+
+// The greedy action of a Q row, by the rule of torch.argmax / np.argmax: the first maximum, and a NaN counts as the maximum.  The one
+// copy: actor_greedy_kernel, the device-resident rollout and the device-resident evaluation call it.
+__device__ __forceinline__ int first_argmax(const float* q, int n) {
+    float best = q[0];
+    int arg = 0;
+    for (int k = 1; k < n; ++k) {
+        const float v = q[k];
+        if (v > best || (v != v && best == best)) {
+            best = v;
+            arg = k;
+        }
+    }
+    return arg;
 }
 
 // Greedy evaluation (dtqn_actor_greedy_batch / dtqn_img_actor_greedy_batch): len_i == 0 marks environment i as idle.

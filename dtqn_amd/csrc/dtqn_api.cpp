@@ -257,8 +257,20 @@ extern "C" int dtqn_actor_greedy_batch(const DtqnNet* net, const float* theta, c
     return dtqn::actor_greedy_rows(h.lens, q_dev, q_last_host, action_host, n_envs, n_max, net->num_actions, s);
 }
 
-// Device-resident rollout (dtqn_rollout.hip): the forward of dtqn_actor_forward_batch on the context block that lives in the rollout
-// state -- no host copy, the ragged lengths are read on the device -- then the one-workgroup step kernel.  Two launches, nothing between.
+// The forward of dtqn_actor_forward_batch on a context block that lives in a device-resident state (`block`: its byte offset in
+// d->state; d: DtqnRollout or DtqnEval, the same field names) -- no host copy, the ragged lengths are read on the device.
+template <class Desc>
+static int resident_forward(const DtqnNet* net, const float* theta, const Desc* d, size_t block, int n_max, int train_mode, uint32_t dropout_seed,
+                            uint32_t dropout_step, void* stream) {
+    if (!theta || !d->q_dev || (!net->tiled && !d->q_last)) return DTQN_ERR_ARG;
+    if (n_max < 1 || n_max > net->ctx_len) return DTQN_ERR_ARG;                 // dtqn.py:170-173
+    const ActorBlock b = actor_block(net, static_cast<uint8_t*>(d->state) + block, d->n_envs);
+    return actor_batch_forward(net, theta, b, d->n_envs, d->n_envs, n_max, d->q_dev, d->q_last, d->workspace, train_mode, dropout_seed, dropout_step,
+                               stream);
+}
+
+// Device-resident rollout (dtqn_rollout.hip): that forward on the block that holds the contexts, then the one-workgroup step kernel.
+// Two launches, nothing between.
 extern "C" int dtqn_rollout_step(const DtqnNet* net, const float* theta, const DtqnReplay* rp, const DtqnRollout* ro, uint32_t vstep, int cur,
                                  int n_max, float epsilon, int store, long long authorize, int run_forward, int train_mode, uint32_t dropout_seed,
                                  uint32_t dropout_step, void* stream) {
@@ -266,30 +278,20 @@ extern "C" int dtqn_rollout_step(const DtqnNet* net, const float* theta, const D
     if (rc != DTQN_OK) return rc;
     if (cur != 0 && cur != 1) return DTQN_ERR_ARG;
     if (run_forward) {
-        if (!theta || !ro->q_dev || (!net->tiled && !ro->q_last)) return DTQN_ERR_ARG;
-        if (n_max < 1 || n_max > net->ctx_len) return DTQN_ERR_ARG;                 // dtqn.py:170-173
-        const dtqn::RolloutLayout l = dtqn::rollout_layout(net, rp, ro);
-        const ActorBlock b = actor_block(net, static_cast<uint8_t*>(ro->state) + l.off[6 + cur], ro->n_envs);
-        rc = actor_batch_forward(net, theta, b, ro->n_envs, ro->n_envs, n_max, ro->q_dev, ro->q_last, ro->workspace, train_mode, dropout_seed,
-                                 dropout_step, stream);
+        rc = resident_forward(net, theta, ro, dtqn::rollout_layout(net, rp, ro).off[6 + cur], n_max, train_mode, dropout_seed, dropout_step, stream);
         if (rc != DTQN_OK) return rc;
     }
     return dtqn::rollout_step_launch(net, rp, ro, vstep, cur, n_max, epsilon, store, authorize, run_forward ? 1 : 0, (hipStream_t)stream);
 }
 
-// Device-resident evaluation (dtqn_deval.hip): the same forward in eval mode (no dropout key is taken) on the context block that lives
-// in the evaluation state, then the one-workgroup step kernel.  Two launches, nothing between.
+// Device-resident evaluation (dtqn_deval.hip): the same in eval mode (no dropout key is taken) on the evaluation's state.
 extern "C" int dtqn_deval_step(const DtqnNet* net, const float* theta, const DtqnEval* ev, uint32_t key, uint32_t step, int cur, int n_max,
                                int episodes, void* stream) {
     int rc = dtqn::deval_check(net, ev);
     if (rc != DTQN_OK) return rc;
     if (cur != 0 && cur != 1) return DTQN_ERR_ARG;
     if (episodes < 0 || episodes > ev->max_episodes) return DTQN_ERR_ARG;
-    if (!theta || !ev->q_dev || (!net->tiled && !ev->q_last)) return DTQN_ERR_ARG;
-    if (n_max < 1 || n_max > net->ctx_len) return DTQN_ERR_ARG;                 // dtqn.py:170-173
-    const dtqn::DevalLayout l = dtqn::deval_layout(net, ev);
-    const ActorBlock b = actor_block(net, static_cast<uint8_t*>(ev->state) + l.off[8 + cur], ev->n_envs);
-    rc = actor_batch_forward(net, theta, b, ev->n_envs, ev->n_envs, n_max, ev->q_dev, ev->q_last, ev->workspace, 0, 0u, 0u, stream);
+    rc = resident_forward(net, theta, ev, dtqn::deval_layout(net, ev).off[8 + cur], n_max, 0, 0u, 0u, stream);
     if (rc != DTQN_OK) return rc;
     return dtqn::deval_step_launch(net, ev, key, step, cur, n_max, episodes, (hipStream_t)stream);
 }

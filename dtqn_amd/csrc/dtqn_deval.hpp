@@ -1,15 +1,14 @@
 // Device-resident greedy evaluation: the layout of its one state allocation and the launches dtqn_api.cpp sequences (dtqn_deval.hip).
+// The environments, the draws and the step bookkeeping it shares with the device-resident rollout are in dtqn_devenv.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "dtqn_actor.hpp"
 #include "dtqn_hip.h"
-#include "dtqn_rollout.hpp"
 
 namespace dtqn {
 
-constexpr int kDevalCounters = 8;
-constexpr int kDevalResultBytes = 24;      // f64 return | i32 length | i32 success | i32 environment | i32 vector step it finished in
+constexpr int kDevalResultBytes = DTQN_DEVAL_RESULT_BYTES;  // f64 return | i32 length | i32 success | i32 environment | i32 vector step it finished in
 
 // Byte offsets of the sections of DtqnEval::state (include/dtqn_hip.h lists them), every section 16-byte aligned.
 struct DevalLayout {
@@ -21,8 +20,9 @@ inline DevalLayout deval_layout(const DtqnNet* net, const DtqnEval* ev) {
     DevalLayout l;
     const size_t N = (size_t)ev->n_envs, O = (size_t)net->obs_dim, K = (size_t)ev->max_episodes;
     l.block_bytes = (actor_block(net, nullptr, ev->n_envs).bytes + 15) & ~(size_t)15;
-    const size_t sizes[DTQN_DEVAL_OFFSETS] = {8 * kDevalCounters, 8 * N * 4,     4 * N * kRolloutEnvInts, 4 * N,         8 * N,        4 * N,
-                                              4 * N * kRolloutLastInts, 4 * N * O, l.block_bytes,          l.block_bytes, kDevalResultBytes * K};
+    const size_t counters = 8 * (DTQN_DEVAL_STATUS_WORDS / 2);        // i64 each: two granules of the status record
+    const size_t sizes[DTQN_DEVAL_OFFSETS] = {counters,                      8 * N * 4, 4 * N * DTQN_DEVENV_STATE_INTS, 4 * N,         8 * N, 4 * N,
+                                              4 * N * DTQN_DEVENV_LAST_INTS, 4 * N * O, l.block_bytes,                  l.block_bytes, kDevalResultBytes * K};
     size_t at = 0;
     for (int k = 0; k < DTQN_DEVAL_OFFSETS; ++k) {
         l.off[k] = at;

@@ -8,7 +8,7 @@ no claim of bit-equality with that package:
   * step(a): s' is drawn from T[a][s], z from O[a][s'], reward = R[a][s][s'][z], done = D[a][s] (the `reset` pairs of the file),
     info["is_success"] = done and reward > 0.
 Every draw is "the first k with u < cdf[k]" on the CDFs the parser derived; `reset_with` / `step_with` take the uniforms, so the
-device-resident environments (csrc/dtqn_rollout.hpp) can be replayed draw for draw.
+device-resident environments (csrc/dtqn_devenv.hpp) can be replayed draw for draw.
 """
 import numpy as np
 from numpy.random import Generator

@@ -416,6 +416,10 @@ int dtqn_debug_last_actor_live(void);
  * A draw is the first k with u < cdf[k]; every CDF row ends in exactly 1.0 from its last positive probability onward. */
 #define DTQN_ROLLOUT_POMDP 2
 #define DTQN_POMDP_SECTIONS 5
+/* Widths both states share (the rollout's and the evaluation's; dtqn_devenv.hpp): i32 words of env_i32 per environment (Memory with 8
+ * pairs: 1 + 16 + 16 <= 40) and of the `last` record. */
+#define DTQN_DEVENV_STATE_INTS 40
+#define DTQN_DEVENV_LAST_INTS 8
 #define DTQN_ROLLOUT_OFFSETS 17
 #define DTQN_ROLLOUT_STATUS_WORDS 16
 typedef struct DtqnRollout {

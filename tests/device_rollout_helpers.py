@@ -29,11 +29,12 @@ def host_env(kind):
 
 def make_agent(lib, device, kind, d_model=64, heads=4, layers=1, gate="res", context=L, slots=E, seed=11, batch=2, q_scale=100.0, sampler="device",
                bag_size=0):
-    """An agent as run.py builds it (get_agent) for the small environment; lib: the emulation library (agent on the CPU) or None."""
+    """An agent as run.py builds it (get_agent) for the small environment; kind: "car" / "mem", or the host environment itself (under
+    its TimeLimit; pomdp_env_helpers.py passes its model's); lib: the emulation library (agent on the CPU) or None."""
     from dtqn_amd.networks.dtqn import DTQN
     from dtqn_amd.utils import agent_utils
     from dtqn_amd.utils.random import set_global_seed
-    env = host_env(kind)
+    env = host_env(kind) if isinstance(kind, str) else kind
     set_global_seed(seed, env)
     cap = env._max_episode_steps
     orig = agent_utils.MODEL_MAP["DTQN"]

@@ -19,6 +19,7 @@ import tempfile
 import numpy as np
 
 from device_rollout_helpers import ROWBLOCK, WHOLE, _patch_emu, check_step_against_host, f32_bits, host_q_rows, replay_arrays
+from device_rollout_helpers import make_agent as rollout_make_agent
 
 __all__ = ["ROWBLOCK", "WHOLE"]
 
@@ -87,32 +88,9 @@ def host_env(cap=CAP):
     return envs.make(MODEL_PATH, max_episode_steps=cap)
 
 
-def make_agent(lib, device, d_model=64, heads=4, layers=1, gate="res", context=L, slots=E, seed=11, batch=2, q_scale=100.0, sampler="device",
-               bag_size=0, cap=CAP):
-    """An agent as run.py builds it (get_agent) for the test model; lib: the emulation library (agent on the CPU) or None."""
-    from dtqn_amd.networks.dtqn import DTQN
-    from dtqn_amd.utils import agent_utils
-    from dtqn_amd.utils.random import set_global_seed
-    env = host_env(cap)
-    set_global_seed(seed, env)
-    orig = agent_utils.MODEL_MAP["DTQN"]
-    if lib is not None:
-        def emu_dtqn(*a, **k):
-            m = DTQN(*a, _test_lib=lib, **k)
-            m._allow_cpu = True
-            return m
-        agent_utils.MODEL_MAP["DTQN"] = emu_dtqn
-    try:
-        agent = agent_utils.get_agent("DTQN", [env], 8, 0, d_model, slots * cap, device, 3e-4, batch, context, cap, context, 1000, 0.99, heads,
-                                      layers, 0.0, False, gate, "learned", bag_size, sampler=sampler, sample_seed=seed)
-    finally:
-        agent_utils.MODEL_MAP["DTQN"] = orig
-    if q_scale != 1.0:        # a fresh Q head gives rows of a few 1e-3: a head 100 x as steep, as after training
-        sd = {k: v.clone() for k, v in agent.policy_network.state_dict().items()}
-        sd["ffn.2.weight"] = sd["ffn.2.weight"] * q_scale
-        agent.policy_network.load_state_dict(sd)
-        agent.target_update()
-    assert agent.replay_buffer.max_size == slots and agent.replay_buffer.max_episode_steps == cap
+def make_agent(lib, device, cap=CAP, **kw):
+    """make_agent of device_rollout_helpers.py (its shapes and keywords) for the test model."""
+    agent = rollout_make_agent(lib, device, host_env(cap), **kw)
     assert agent.env_obs_length == 1 and agent.obs_mask == 4 and agent.num_actions == 3 and agent.is_discrete_env
     return agent
 
