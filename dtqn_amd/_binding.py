@@ -74,6 +74,7 @@ DtqnReplay = _make("DtqnReplay")
 DtqnReplayRecord = _make("DtqnReplayRecord")
 DtqnTd = _make("DtqnTd")
 DtqnRollout = _make("DtqnRollout")
+DtqnDevBag = _make("DtqnDevBag")
 DtqnEval = _make("DtqnEval")
 
 
@@ -110,6 +111,12 @@ def load_library(path: str) -> ctypes.CDLL:
         "dtqn_rollout_commit": [P(DtqnNet), P(DtqnReplay), P(DtqnRollout), u32, ctypes.c_longlong, vp],
         "dtqn_rollout_get_state": [P(DtqnNet), P(DtqnReplay), P(DtqnRollout), vp, vp],
         "dtqn_rollout_set_state": [P(DtqnNet), P(DtqnReplay), P(DtqnRollout), vp, vp],
+        "dtqn_devbag_state_bytes": [P(DtqnNet), P(DtqnDevBag), vp],
+        "dtqn_rollout_reset_bag": [P(DtqnNet), P(DtqnReplay), P(DtqnRollout), P(DtqnDevBag), u32, vp],
+        "dtqn_rollout_step_bag": [P(DtqnNet), vp, P(DtqnReplay), P(DtqnRollout), P(DtqnDevBag), u32, i32, i32, ctypes.c_float, i32, ctypes.c_longlong, i32,
+                                  i32, u32, u32, i32, vp],
+        "dtqn_devbag_get_state": [P(DtqnNet), P(DtqnDevBag), vp, vp],
+        "dtqn_devbag_set_state": [P(DtqnNet), P(DtqnDevBag), vp, vp],
         "dtqn_deval_state_bytes": [P(DtqnNet), P(DtqnEval), vp],
         "dtqn_deval_begin": [P(DtqnNet), P(DtqnEval), u32, i32, vp],
         "dtqn_deval_step": [P(DtqnNet), vp, P(DtqnEval), u32, u32, i32, i32, i32, vp],
@@ -177,7 +184,7 @@ def load_library(path: str) -> ctypes.CDLL:
             ctypes.c_longlong if name in ("dtqn_img_act_floats", "dtqn_img_gact_floats", "dtqn_img_wpart_floats",
                                                     "dtqn_grad_workspace_floats", "dtqn_img_actor_stage_bytes",
                                                     "dtqn_img_actor_workspace_floats", "dtqn_rollout_state_bytes", "dtqn_pomdp_table_bytes",
-                                                    "dtqn_deval_state_bytes") else ctypes.c_int)
+                                                    "dtqn_deval_state_bytes", "dtqn_devbag_state_bytes") else ctypes.c_int)
     assert set(protos) == set(FUNCTIONS), sorted(set(protos) ^ set(FUNCTIONS))
     if lib.dtqn_abi_version() != DEFINES["DTQN_ABI_VERSION"]:
         raise OSError(f"{path}: ABI version {lib.dtqn_abi_version()} != header {DEFINES['DTQN_ABI_VERSION']}")

@@ -59,13 +59,14 @@ class DeviceEnvs:
     ENTRY, DESC = "", None                         # prefix of its entry points (dtqn_rollout / dtqn_deval), its descriptor type
     COUNTERS, RETURN_SUM = (), 0                   # names of the status record's counters; which one is the f64 return sum
     LAST_SECTION, BLOCK_SECTION = 0, 0             # state sections of the `last` record and of actor block 0 (block 1 follows)
+    BAGS = False                                   # a subclass that keeps the bags on the device (device_bag.py) says True
 
     def __init__(self, agent, env_id: str, n_envs: int, seed: int, max_episode_steps: Optional[int], num_pairs: Optional[int]):
         what = self.WHAT
         env, kind = make_device_env(env_id, max_episode_steps, f"{what} (use {self.FLAG} otherwise)")
         if getattr(agent, "image", None) is not None:
             raise NotImplementedError(f"device-resident {what}: image networks are not covered (use {self.FLAG})")
-        if agent.bag.size > 0:
+        if agent.bag.size > 0 and not self.BAGS:
             raise NotImplementedError(f"device-resident {what}: bag networks are not covered (use {self.FLAG})")
         if agent.dp is not None or ddp.is_distributed():
             raise NotImplementedError(f"device-resident {what}: data-parallel runs are not covered")

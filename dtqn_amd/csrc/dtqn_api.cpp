@@ -5,6 +5,7 @@
 
 #include "dtqn_actor.hpp"
 #include "dtqn_deval.hpp"
+#include "dtqn_devbag.hpp"
 #include "dtqn_hip.h"
 #include "dtqn_limits.h"
 #include "dtqn_rollout.hpp"
@@ -282,6 +283,52 @@ extern "C" int dtqn_rollout_step(const DtqnNet* net, const float* theta, const D
         if (rc != DTQN_OK) return rc;
     }
     return dtqn::rollout_step_launch(net, rp, ro, vstep, cur, n_max, epsilon, store, authorize, run_forward ? 1 : 0, (hipStream_t)stream);
+}
+
+// The rollout's and the bag descriptor's checks for the bag entry points: DTQN_ERR_CONFIG for a network without a bag.
+static int rollout_bag_check(const DtqnNet* net, const DtqnReplay* rp, const DtqnRollout* ro, const DtqnDevBag* bag) {
+    if (!bag) return DTQN_ERR_ARG;
+    const int rc = dtqn::rollout_check_bags(net, rp, ro);
+    return rc != DTQN_OK ? rc : dtqn::devbag_check(net, ro, bag);
+}
+
+extern "C" int dtqn_rollout_reset_bag(const DtqnNet* net, const DtqnReplay* rp, const DtqnRollout* ro, const DtqnDevBag* bag, uint32_t vstep,
+                                      void* stream) {
+    int rc = rollout_bag_check(net, rp, ro, bag);
+    if (rc != DTQN_OK) return rc;
+    if ((rc = dtqn::rollout_reset_launch(net, rp, ro, vstep, (hipStream_t)stream)) != DTQN_OK) return rc;
+    return dtqn::devbag_stage_launch(net, rp, ro, bag, 0, 1, 0, (hipStream_t)stream);
+}
+
+// Device-resident rollout of a bag network (dtqn_devbag.hip): up to five launches, nothing between -- the actor forward with the bags,
+// the rollout's step kernel, the bags' bookkeeping, and where a choice can be due the candidate forward and the selection.
+extern "C" int dtqn_rollout_step_bag(const DtqnNet* net, const float* theta, const DtqnReplay* rp, const DtqnRollout* ro, const DtqnDevBag* bag,
+                                     uint32_t vstep, int cur, int n_max, float epsilon, int store, long long authorize, int run_forward,
+                                     int train_mode, uint32_t dropout_seed, uint32_t dropout_step, int may_choose, void* stream) {
+    int rc = rollout_bag_check(net, rp, ro, bag);
+    if (rc != DTQN_OK) return rc;
+    if (cur != 0 && cur != 1) return DTQN_ERR_ARG;
+    if (!theta || !ro->q_dev) return DTQN_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    const dtqn::RolloutLayout l = dtqn::rollout_layout(net, rp, ro);
+    const dtqn::DevBagViews v = dtqn::devbag_views(net, bag);
+    const int N = ro->n_envs, L = net->ctx_len;
+    if (run_forward) {
+        if (n_max < 1 || n_max > L) return DTQN_ERR_ARG;                        // dtqn.py:170-173
+        const ActorBlock b = actor_block(net, static_cast<uint8_t*>(ro->state) + l.off[6 + cur], N);
+        rc = dtqn::tiled_forward_bag_resident(net, theta, b.obs, b.actions, v.bag_obs, v.bag_act, N, n_max, L, ro->q_dev, bag->workspace, train_mode,
+                                              dropout_seed, dropout_step, s, b.lens, nullptr, nullptr);
+        if (rc != DTQN_OK) return rc;
+    }
+    if ((rc = dtqn::rollout_step_launch(net, rp, ro, vstep, cur, n_max, epsilon, store, authorize, run_forward ? 1 : 0, s)) != DTQN_OK) return rc;
+    if ((rc = dtqn::devbag_stage_launch(net, rp, ro, bag, cur, 0, may_choose ? 1 : 0, s)) != DTQN_OK) return rc;
+    if (!may_choose) return DTQN_OK;
+    // the K + 1 candidate bags of environment i on its one context after the transition: the full L rows of the block the step wrote
+    const ActorBlock out = actor_block(net, static_cast<uint8_t*>(ro->state) + l.off[6 + (cur ^ 1)], N);
+    rc = dtqn::tiled_forward_bag_resident(net, theta, out.obs, out.actions, v.cand_obs, v.cand_act, N * (net->bag_size + 1), L, L, bag->q_cand,
+                                          bag->workspace, 0, 0u, 0u, s, nullptr, v.seq_ctx, v.seq_start);
+    if (rc != DTQN_OK) return rc;
+    return dtqn::devbag_select_launch(net, bag, s);
 }
 
 // Device-resident evaluation (dtqn_deval.hip): the same in eval mode (no dropout key is taken) on the evaluation's state.

@@ -359,10 +359,11 @@ __device__ __forceinline__ void env_post(const DevEnvArgs& a, uint32_t tag32, co
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------------
 // DTQN_OK when the environment fields of a descriptor (DtqnRollout, DtqnEval: the same names) fit the network: flat f32 observations of
-// the environment's width, its action count, at most 255 actions (a u8 per action); DTQN_ERR_CONFIG for an image or a bag network.
+// the environment's width, its action count, at most 255 actions (a u8 per action); DTQN_ERR_CONFIG for an image or a bag network
+// (bags != 0: a bag network passes -- the entry points that serve dtqn_devbag.hip's path ask so).
 template <class Desc>
-inline int devenv_check(const DtqnNet* net, const Desc* d) {
-    if (net->img_c > 0 || net->bag_size > 0) return DTQN_ERR_CONFIG;
+inline int devenv_check(const DtqnNet* net, const Desc* d, int bags = 0) {
+    if (net->img_c > 0 || (net->bag_size > 0 && !bags)) return DTQN_ERR_CONFIG;
     if (d->max_episode_steps < 1) return DTQN_ERR_ARG;
     if (d->env_kind == DTQN_ROLLOUT_CARFLAG) {
         if (net->obs_dim != 3 || net->num_actions != 3) return DTQN_ERR_ARG;

@@ -193,13 +193,16 @@ static RolloutArgs rollout_args(const DtqnNet* net, const DtqnReplay* rp, const 
 }
 
 // The environment check, then what is the rollout's: the replay it writes into, and an episode that fits its staging and its slot.
-int rollout_check(const DtqnNet* net, const DtqnReplay* rp, const DtqnRollout* ro) {
+static int rollout_check_net(const DtqnNet* net, const DtqnReplay* rp, const DtqnRollout* ro, int bags) {
     if (!net || !rp || !ro || !ro->state || !ro->status_host || ro->n_envs < 1 || ro->pending_slots < 1) return DTQN_ERR_ARG;
-    const int rc = devenv_check(net, ro);
+    const int rc = devenv_check(net, ro, bags);
     if (rc == DTQN_ERR_CONFIG || rp->obs_u8 != nullptr || !rp->obs || !rp->actions || !rp->rewards || !rp->dones || !rp->ep_len) return DTQN_ERR_CONFIG;
     if (rc != DTQN_OK || rp->obs_dim != net->obs_dim || rp->num_episodes < 1 || ro->pos0 < 0 || ro->max_episode_steps > rp->max_steps) return DTQN_ERR_ARG;
     return DTQN_OK;
 }
+int rollout_check(const DtqnNet* net, const DtqnReplay* rp, const DtqnRollout* ro) { return rollout_check_net(net, rp, ro, 0); }
+// The twin that admits a bag network: the bag path's entry points (dtqn_api.cpp) and commit / get_state / set_state, which launch no forward.
+int rollout_check_bags(const DtqnNet* net, const DtqnReplay* rp, const DtqnRollout* ro) { return rollout_check_net(net, rp, ro, 1); }
 
 int rollout_reset_launch(const DtqnNet* net, const DtqnReplay* rp, const DtqnRollout* ro, uint32_t vstep, hipStream_t stream) {
     return devenv_launch(dtqn_rollout_reset_kernel, rollout_args(net, rp, ro, vstep, 1), stream);        // a reset writes the `out` block: block 0
@@ -247,15 +250,15 @@ extern "C" int dtqn_rollout_reset(const DtqnNet* net, const DtqnReplay* rp, cons
 }
 
 extern "C" int dtqn_rollout_commit(const DtqnNet* net, const DtqnReplay* rp, const DtqnRollout* ro, uint32_t vstep, long long authorize, void* stream) {
-    const int rc = rollout_check(net, rp, ro);
+    const int rc = rollout_check_bags(net, rp, ro);
     return rc != DTQN_OK ? rc : rollout_commit_launch(net, rp, ro, vstep, authorize, (hipStream_t)stream);
 }
 
 extern "C" int dtqn_rollout_get_state(const DtqnNet* net, const DtqnReplay* rp, const DtqnRollout* ro, void* host, void* stream) {
-    if (!host || rollout_check(net, rp, ro) != DTQN_OK) return DTQN_ERR_ARG;
+    if (!host || rollout_check_bags(net, rp, ro) != DTQN_OK) return DTQN_ERR_ARG;
     return devenv_copy_state(host, ro->state, rollout_layout(net, rp, ro).bytes, hipMemcpyDeviceToHost, stream);
 }
 extern "C" int dtqn_rollout_set_state(const DtqnNet* net, const DtqnReplay* rp, const DtqnRollout* ro, const void* host, void* stream) {
-    if (!host || rollout_check(net, rp, ro) != DTQN_OK) return DTQN_ERR_ARG;
+    if (!host || rollout_check_bags(net, rp, ro) != DTQN_OK) return DTQN_ERR_ARG;
     return devenv_copy_state(ro->state, host, rollout_layout(net, rp, ro).bytes, hipMemcpyHostToDevice, stream);
 }

@@ -34,6 +34,8 @@ inline RolloutLayout rollout_layout(const DtqnNet* net, const DtqnReplay* rp, co
 
 // DTQN_OK when the descriptor, the network and the replay fit the kernels (flat f32 observations of the environment's width, ...)
 int rollout_check(const DtqnNet* net, const DtqnReplay* rp, const DtqnRollout* ro);
+// ... and the same check for the callers that admit a bag network (dtqn_devbag.hpp)
+int rollout_check_bags(const DtqnNet* net, const DtqnReplay* rp, const DtqnRollout* ro);
 int rollout_reset_launch(const DtqnNet* net, const DtqnReplay* rp, const DtqnRollout* ro, uint32_t vstep, hipStream_t stream);
 // q_rows: where the step kernel finds Q of the last live row -- q_last [N][A] (stride 0) or q_dev with n_max rows per sequence
 int rollout_step_launch(const DtqnNet* net, const DtqnReplay* rp, const DtqnRollout* ro, uint32_t vstep, int cur, int n_max, float epsilon,

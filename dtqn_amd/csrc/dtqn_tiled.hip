@@ -4558,8 +4558,9 @@ extern "C" int dtqn_forward_workspace_floats(const DtqnNet* net, int batch) {
 static int forward_tiled_impl(const DtqnNet* net, const float* theta, const float* obs, const uint8_t* actions, const float* bag_obs,
                               const uint8_t* bag_actions, int batch, int n, int in_rows, float* q_out, float* workspace, void* stream,
                               int train_mode = 0, uint32_t drop_seed = 0u, uint32_t drop_step = 0u, const int32_t* lens = nullptr,
-                              const float* pre = nullptr) {
+                              const float* pre = nullptr, const int32_t* seq_src = nullptr, const int32_t* seq_start = nullptr) {
     if (!net || !theta || (!obs && !pre) || !q_out || !workspace || batch < 1) return DTQN_ERR_ARG;
+    if ((seq_src == nullptr) != (seq_start == nullptr)) return DTQN_ERR_ARG;
     if (n < 1 || n > net->ctx_len || in_rows < n) return DTQN_ERR_ARG;  // dtqn.py:170-173
     if (net->action_dim > 0 && !actions) return DTQN_ERR_ARG;
     if (!net->tiled) return DTQN_ERR_CONFIG;
@@ -4568,7 +4569,9 @@ static int forward_tiled_impl(const DtqnNet* net, const float* theta, const floa
     EmbedSrc src;
     src.obs = obs; src.actions = actions;
     src.obs_ep_stride = (long long)in_rows * net->obs_dim; src.act_ep_stride = in_rows;
-    src.ep_idx = nullptr; src.start = nullptr; src.batch = batch;
+    // seq_src / seq_start (device [batch] each): sequence s reads source sequence seq_src[s] from row seq_start[s] -- the embedding's
+    // window addressing with one pass of `batch` sequences; nullptr: sequence s reads source s from row 0
+    src.ep_idx = seq_src; src.start = seq_start; src.batch = batch;
     src.bag_obs = bag_obs; src.bag_actions = bag_actions; src.bag_batch = batch;
     src.lens = lens;
     src.pre = pre; src.pre_rows = n;
@@ -4591,6 +4594,16 @@ int tiled_forward_actor(const DtqnNet* net, const float* theta, const float* obs
     if (net && net->bag_size > 0) return DTQN_ERR_ARG;
     return forward_tiled_impl(net, theta, obs, actions, nullptr, nullptr, batch, n, in_rows, q_out, workspace, stream, train_mode, drop_seed,
                               drop_step, lens);
+}
+// The forward of a bag network on resident arrays (dtqn_rollout_step_bag): `batch` sequences with one bag each, ragged prefixes (lens) or
+// whole contexts; seq_src / seq_start as forward_tiled_impl's (the K + 1 candidate bags of an environment share its one context).
+int tiled_forward_bag_resident(const DtqnNet* net, const float* theta, const float* obs, const uint8_t* actions, const float* bag_obs,
+                               const uint8_t* bag_actions, int batch, int n, int in_rows, float* q_out, float* workspace, int train_mode,
+                               uint32_t drop_seed, uint32_t drop_step, hipStream_t stream, const int32_t* lens, const int32_t* seq_src,
+                               const int32_t* seq_start) {
+    if (!net || net->bag_size < 1) return DTQN_ERR_ARG;
+    return forward_tiled_impl(net, theta, obs, actions, bag_obs, bag_actions, batch, n, in_rows, q_out, workspace, stream, train_mode, drop_seed,
+                              drop_step, lens, nullptr, seq_src, seq_start);
 }
 }  // namespace dtqn
 

@@ -465,6 +465,52 @@ int dtqn_rollout_commit(const DtqnNet* net, const DtqnReplay* rp, const DtqnRoll
 int dtqn_rollout_get_state(const DtqnNet* net, const DtqnReplay* rp, const DtqnRollout* ro, void* host, void* stream);
 int dtqn_rollout_set_state(const DtqnNet* net, const DtqnReplay* rp, const DtqnRollout* ro, const void* host, void* stream);
 /* ------------------------------------------------------------------------------------------
+ * Device-resident rollout of a bag network (dtqn_devbag.hip; DESIGN.md "Device-resident bags"): one persistent-memory bag per
+ * environment in a device allocation of its own, next to the DtqnRollout state.  The actor forward takes the bags; what a full
+ * context evicts is appended to its environment's bag, and a full bag keeps the best of its K + 1 candidate contents by the policy
+ * network's mean-over-time max-Q (dtqn/agents/dtqn.py:125-157) -- a batched forward over N (K + 1) sequences and a reduction, nothing
+ * read back.  dtqn_rollout_reset / _step / dtqn_deval_* keep refusing bag networks (DTQN_ERR_CONFIG); dtqn_rollout_commit / _get_state /
+ * _set_state serve both.  K = net->bag_size, N = n_envs, O = obs_dim, L = ctx_len, A = num_actions.
+ * state layout (byte offsets from dtqn_devbag_state_bytes, every section 16-byte aligned):
+ *   [0] bag_obs   f32[N][K][O]        [1] bag_act  u8[N][K]        [2] bag_pos  i32[N]   entries in the bag (0 .. K)
+ *   [3] cand_obs  f32[N][K+1][K][O]   [4] cand_act u8[N][K+1][K]   candidate c < K: entry c replaced by the evicted pair; candidate K: the bag
+ *   [5] choosing  i32[N]              1 between the stage and the select kernel of a step in which environment i chooses
+ *   [6] scores    f32[N][K+1]         mean over the L rows of max_a Q, of the last choice of environment i
+ *   [7] choice    i32[N]              the candidate kept in the last step; -1 = no choice in that step
+ *   [8] counters  i64[4]              appends | choices | choices that kept the bag as it was | bags cleared by an episode end
+ *   [9] seq_ctx   i32[2][N (K+1)]     candidate sequence s reads context seq_ctx[0][s] = s / (K+1) from row seq_ctx[1][s] = 0 (rewritten
+ *                                     by every launch: the index table of the candidate forward's embedding)
+ * Bag actions (and candidate actions) index the action embedding: whoever writes a state keeps them below A.
+ * ------------------------------------------------------------------------------------------ */
+#define DTQN_DEVBAG_OFFSETS 10
+#define DTQN_DEVBAG_COUNTERS 4
+#define DTQN_DEVBAG_MAX_CANDIDATES 513
+typedef struct DtqnDevBag {
+    void* state;                      /* device, dtqn_devbag_state_bytes() bytes, zeroed once by the caller */
+    float* q_cand;                    /* device [N (K+1)][L][A]: Q of the candidate forward */
+    float* workspace;                 /* dtqn_forward_workspace_floats(net, N (K+1)) floats; the actor forward may share it */
+    int32_t n_envs;                   /* N: equals DtqnRollout::n_envs */
+    float obs_mask;                   /* padding value of an empty bag entry (Bag.make_empty_bag) */
+} DtqnDevBag;
+/* Bytes of DtqnDevBag::state; offsets (may be NULL): int32[DTQN_DEVBAG_OFFSETS] byte offsets of the sections above.  < 0: bad arguments. */
+long long dtqn_devbag_state_bytes(const DtqnNet* net, const DtqnDevBag* bag, int32_t* offsets);
+/* dtqn_rollout_reset, plus: every bag cleared (obs_mask / action 0 / pos 0), the candidate slots initialised to the cleared bag. */
+int dtqn_rollout_reset_bag(const DtqnNet* net, const DtqnReplay* rp, const DtqnRollout* ro, const DtqnDevBag* bag, uint32_t vstep, void* stream);
+/* One vector step of a bag network, all on `stream`, nothing between: the actor forward on block `cur` with the bags (run_forward != 0;
+ * the whole bag, padding included, as get_action), dtqn_rollout_step's step kernel, dtqn_devbag_stage_kernel (episode ended: bag cleared;
+ * window slid: the evicted pair is appended, or with a full bag the K + 1 candidates are written), and with may_choose != 0 the candidate
+ * forward over N (K+1) sequences of the L rows of block cur ^ 1 and dtqn_devbag_select_kernel (scores, first arg-max, that candidate
+ * becomes the bag).  may_choose: the caller sets it when an environment can have a full context and a full bag after this step (vector
+ * steps since the reset + 1 >= L + K); with may_choose == 0 a pair evicted onto a full bag is dropped.  Every other argument as
+ * dtqn_rollout_step.  DTQN_ERR_CONFIG: no bag, dropout > 0 (the candidate forward would need a dropout key of its own), or more than
+ * DTQN_DEVBAG_MAX_CANDIDATES candidates. */
+int dtqn_rollout_step_bag(const DtqnNet* net, const float* theta, const DtqnReplay* rp, const DtqnRollout* ro, const DtqnDevBag* bag,
+                          uint32_t vstep, int cur, int n_max, float epsilon, int store, long long authorize, int run_forward, int train_mode,
+                          uint32_t dropout_seed, uint32_t dropout_step, int may_choose, void* stream);
+/* Copy the whole bag state to / from host memory (asynchronous on `stream`; pinned memory keeps it so). */
+int dtqn_devbag_get_state(const DtqnNet* net, const DtqnDevBag* bag, void* host, void* stream);
+int dtqn_devbag_set_state(const DtqnNet* net, const DtqnDevBag* bag, const void* host, void* stream);
+/* ------------------------------------------------------------------------------------------
  * Device-resident greedy evaluation (dtqn_deval.hip; DESIGN.md "Device-resident evaluation"): a quota of `episodes` greedy episodes
  * played by N CarFlag, Memory or tabular POMDP environments in ONE device allocation (`state`).  Environment i plays episodes i, i + N, ...; with
  * none left it goes idle (len = 1, no step, never counted).  Every draw of an episode is a function of (seed, key, episode index,

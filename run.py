@@ -77,7 +77,10 @@ def get_args(argv: Optional[Sequence[str]] = None):
     p.add_argument("--device-envs", type=int, default=0,
                    help="device-resident rollout (dtqn_amd.agents.device_rollout.DeviceVectorActor): N > 0 steps N CarFlag / Memory / "
                         "tabular POMDP environments on the GPU behind the batched actor forward, prepopulation included; the loop is that of "
-                        "--num-envs (N updates per vector step).  Needs --sampler device; 0 = off")
+                        "--num-envs (N updates per vector step).  Needs --sampler device; 0 = off.  With --bag-size K > 0 the bags live on "
+                        "the GPU too (dtqn_amd.agents.device_bag.DeviceBagVectorActor: appended, and chosen among K + 1 candidates by a "
+                        "batched forward, with nothing read back); evaluation of a bag run stays on the host (--eval-envs), "
+                        "--device-eval-envs refuses it")
     p.add_argument("--overlap", action="store_true",
                    help="pipeline the actor forward of step t+1 with TD update t+1 on two HIP streams (same policy-vs-action "
                         "semantics; an episode that ends at step t becomes sampleable one update later)")
@@ -281,10 +284,14 @@ def run_experiment(args):
         if len(args.envs) != 1:
             raise NotImplementedError("--device-envs steps copies of ONE training domain")
         from dtqn_amd.agents.device_rollout import DeviceVectorActor
+        actor_cls = DeviceVectorActor
+        if args.bag_size > 0:                      # the bags on the device as well; evaluation goes through evaluate() / --eval-envs
+            from dtqn_amd.agents.device_bag import DeviceBagVectorActor
+            actor_cls = DeviceBagVectorActor
         # the step cap is the registry entry's; an explicit --max-episode-steps (it sizes the replay's rows) caps the device
         # environments as well, so that an episode always fits its slot
-        vector = DeviceVectorActor(agent, args.envs[0], args.device_envs, args.seed + 1000 * (rank + 1),
-                                   max_episode_steps=args.max_episode_steps if args.max_episode_steps > 0 else None)
+        vector = actor_cls(agent, args.envs[0], args.device_envs, args.seed + 1000 * (rank + 1),
+                           max_episode_steps=args.max_episode_steps if args.max_episode_steps > 0 else None)
     if os.path.exists(policy_path + "_mini_checkpoint.pt"):
         done_steps = agent.load_mini_checkpoint(policy_path)["step"]
         print(f"Found a mini checkpoint that completed {done_steps} training steps.")
