@@ -152,10 +152,16 @@ def engine_probe(cfg, net, eng):
     return {"masks": masks, "argmax": torch.from_numpy(q3[1].argmax(-1))}
 
 
+ADAM_CHECK_TOTALS = [0.0, 0]         # seconds spent in / number of the per-step optimizer checks of check_td_updates, this process
+
+
 def check_td_updates(cfg, net, oracle, host, eng, rep, n_updates, q_tol=1e-4, grad_rtol=2e-4, one_call=False, q_rel=False,
                      pipelined=False, draw_seed=1234, report_as=None):
     """Run n_updates on both sides from identical (episode, start) draws and compare every stage:
     the three Q tensors, pre-clip gradients, statistics, parameters after the step.
+    Every step is also an optimizer check on its own: the engine's post-step theta, exp_avg and exp_avg_sq against the float64
+    reference of adam_f64_helpers.py (clip + torch.optim.Adam) run on the engine's OWN pre-step state, gradient and reported norm,
+    within the rounding bounds derived there -- the optimizer apart from the gradient error bounded above.
     one_call: the whole update through dtqn_td_update, as the agent's train() issues it, instead of stage by stage;
     everything compared is still left behind by that call.
     pipelined: the update as DtqnAgent.train() issues it with the device sampler (dtqn_amd/learner.py: the window draw inside the
@@ -166,8 +172,16 @@ def check_td_updates(cfg, net, oracle, host, eng, rep, n_updates, q_tol=1e-4, gr
     keys = O.trainable_keys(cfg)
     Bn, L, A = eng.batch, cfg.history_len, cfg.num_actions
     net = eng.net                  # the net the update runs on: the caller's, or its row-block twin (dtqn_td_prefers_tiled)
-    worst = {"q_abs_err": 0.0, "q_abs_max": 0.0, "grad_err_over_max": 0.0, "updates": n_updates}
+    worst = {"q_abs_err": 0.0, "q_abs_max": 0.0, "grad_err_over_max": 0.0, "updates": n_updates,
+             "adam_theta_over_bound": 0.0, "adam_m_over_bound": 0.0, "adam_v_over_bound": 0.0, "adam_check_seconds": 0.0}
+    import time
+    from adam_f64_helpers import check_against_r32h, hyper_of
+    nt = net.n_trainable
+    # the engine's pre-step optimizer state: taken here in the modes that step inside one call (the moments are then the zeros /
+    # oracle values written below), in front of clip_adam otherwise
+    snapshot = lambda: (eng.theta_pol.cpu().numpy()[:nt].copy(), eng.adam_m.cpu().numpy().copy(), eng.adam_v.cpu().numpy().copy())
     for it in range(n_updates):
+        snap = snapshot()
         if pipelined:
             assert getattr(eng, "_pipe", None) is not None and cfg.bag_size == 0 and cfg.dropout == 0
             n_valid, exclude = min(host.pos[0], host.max_size), host.pos[0] % host.max_size
@@ -239,8 +253,21 @@ def check_td_updates(cfg, net, oracle, host, eng, rep, n_updates, q_tol=1e-4, gr
             assert not got[:net.n_trainable][pad].any(), (it, int(np.count_nonzero(got[:net.n_trainable][pad])))
         # --- optimizer step + statistics
         if not one_call and not pipelined:
+            snap = snapshot()
             eng.clip_adam()
         st = eng.read_stats()
+        t0 = time.perf_counter()
+        hp = hyper_of(eng)
+        assert hp.grad_scale == 1.0 and int(eng.td.grad) == eng.grad.data_ptr()      # the gradient the step used is eng.grad
+        got_m, got_v = eng.adam_m.cpu().numpy().copy(), eng.adam_v.cpu().numpy().copy()
+        r, _, _ = check_against_r32h(snap[0], snap[1], snap[2], got[:nt], st["grad_norm"], it + 1, hp,
+                                     eng.theta_pol.cpu().numpy()[:nt], got_m, got_v, what=("optimizer step", it))
+        for key in ("theta", "m", "v"):
+            worst[f"adam_{key}_over_bound"] = max(worst[f"adam_{key}_over_bound"], r[key])
+        assert not got_m[pad].any() and not got_v[pad].any()      # the moments of the width padding stay exactly zero
+        worst["adam_check_seconds"] += time.perf_counter() - t0
+        ADAM_CHECK_TOTALS[0] += time.perf_counter() - t0
+        ADAM_CHECK_TOTALS[1] += 1
         # teacher-force the oracle from the engine's pre-step parameters?  No: both sides started
         # identical and took identical steps so far; compare the step itself on solid elements.
         ref_stats = oracle.update(batch, grads_and_out=(grads, out))
