@@ -174,9 +174,38 @@ __global__ __launch_bounds__(NW * 64) void dtqn_backward_kernel(BwdArgs a, Ahead
     const int ep = a.ep_idx[b], st0 = a.start[b] + R0;
     Drop dr = drop_off();
     if constexpr (DROP) dr = Drop{a.drop_thresh, a.drop_scale, a.drop_seed, (uint32_t)a.step_counter[1], (uint32_t)b};
-    int ps = 0;
-    DTQN_PROF(a.prof, ps++);
-    // everything the head stage needs goes in flight before the (latency-bound, one-wave) loss stage
+    // Stage marks.  The prologue's (kernel entry .. "LN2 bwd done" of the top layer, and the finer marks in slots 20..23 and 24..31) are
+    // deferred stamps: the clock is read into a scalar register on the spot and stored behind the kernel's last barrier, so that no store
+    // (and no wait the compiler puts in front of one) sits between the prologue's loads and their use.  The steady stages keep DTQN_PROF.
+    enum { PK_ENTRY, PK_PREFETCH, PK_LOSS_LOADS, PK_LOSS_WAVE, PK_LOSS_BARRIER, PK_LOSS, PK_HEAD2, PK_HEAD, PK_DH_PREFETCH,
+           PK_STATS, PK_S2_BEFORE, PK_S2_LDS, PK_S2_BARRIER, PK_LN2_BODY, PK_LN2, PK_N };
+    long long pclk[PK_N] = {};
+    int ps = 4;                    // slots 0 .. 2 and the top layer's 3 come from pclk
+    DTQN_PROF_CLOCK(pclk[PK_ENTRY]);
+    // ---------------- B0, first half: the loss rows go in flight ----------------
+    // The loss wave's round trip (actions | rewards | dones of this slice's rows -- replay rows no earlier kernel of the update touched --
+    // and its three Q rows) is what the whole chain waits for first, and loads return in issue order: it is issued in front of the
+    // prefetch batch, by every lane of the loss wave alike (td_loss_issue: rows outside the loss window read the window's first row).
+    // (One wave-uniform branch: with the other seven waves issuing the same loads, 48 of the 80 instantiations took 1 - 6 VGPRs more
+    //  and the headline one 234 instead of 231.  The loss wave's waits stay counted: vmcnt(N) with N the loads it issued behind these.)
+    static_assert(LP <= 64, "one loss row per lane of one wave");
+    const float* q0 = a.q3 + (((size_t)0 * a.batch + b) * LPF + R0) * AP;
+    const float* q1 = a.q3 + (((size_t)1 * a.batch + b) * LPF + R0) * AP;
+    const float* q2 = a.q3 + (((size_t)2 * a.batch + b) * LPF + R0) * AP;
+    TdLossRow lrow = {};
+    if (t.wave == 0)
+        td_loss_issue(lrow, q0, q1, q2, AP, Lfull - R0, LP, a.history, -R0,       // window test in slice-local rows
+                      a.actions + (size_t)ep * a.act_ep_stride + st0, a.rewards + (size_t)ep * a.rew_ep_stride + st0,
+                      a.dones + (size_t)ep * a.rew_ep_stride + st0, t.lane);
+    DTQN_SCHED_FENCE();
+    DTQN_PROF_CLOCK(pclk[PK_LOSS_LOADS]);
+    // head.2 [A][D] goes through LDS (W5 is free until the first FFN stage): one float4 per thread in flight with the prefetch batch,
+    // stored in front of the barrier that ends the loss stage, so the head stage reads no global memory at all
+    const float* __restrict__ W2h = theta + net.off_head2_w;
+    const int h2n4 = A * (D / 4);
+    static_assert(LPF * LD5 >= DTQN_MAX_ACTIONS * D, "head.2 fits the wide temp");
+    const float4 h2 = ld4(W2h + 4 * (t.tid < h2n4 ? t.tid : 0));
+    // everything else the head stage needs goes in flight before the (latency-bound, one-wave) loss stage
     // delta = dO . o per (row, head) comes out of the dO product's epilogue: a head inside one 16-column tile is summed across its lanes;
     // head width 32 spans two tiles (two different waves): each adds its half into the zero-filled entry -- two addends, so the sum
     // does not depend on who comes first
@@ -202,21 +231,16 @@ __global__ __launch_bounds__(NW * 64) void dtqn_backward_kernel(BwdArgs a, Ahead
 
     // ---------------- B0: double-DQN target, loss, dL/dQ, statistics (dtqn.py:219-253) ----------------
     {
-        const float* q0 = a.q3 + (((size_t)0 * a.batch + b) * LPF + R0) * AP;
-        const float* q1 = a.q3 + (((size_t)1 * a.batch + b) * LPF + R0) * AP;
-        const float* q2 = a.q3 + (((size_t)2 * a.batch + b) * LPF + R0) * AP;
         const float inv_count = 1.0f / ((float)a.batch * (float)a.history);
-        DTQN_PROF(a.prof, 24);   // (finer marks of the stages that carry a first-trip penalty: slots 24..30, printed raw by stage_profile.py)
-        for (int idx = t.tid; idx < LP * AP; idx += NT) dq_s[idx] = 0.f;
-        __syncthreads();
-        DTQN_PROF(a.prof, 25);
+        DTQN_PROF_CLOCK(pclk[PK_PREFETCH]);   // (finer marks of the stages that carry a first-trip penalty: printed raw by tests/perf/stage_profile_bwd_prologue.py)
+        // (no zero-fill of dq_s and no barrier for it: the loss wave writes every entry of its LP rows, zeros included)
         if (t.wave == 0)
-            td_loss_wave(q0, q1, q2, AP, A, Lfull - R0, LP, a.history, a.gamma, inv_count,     // window test in slice-local rows
-                         a.actions + (size_t)ep * a.act_ep_stride + st0, a.rewards + (size_t)ep * a.rew_ep_stride + st0,
-                         a.dones + (size_t)ep * a.rew_ep_stride + st0, dq_s, a.stats_partial + ((size_t)b * RS + slice) * 8, t.lane);
-        DTQN_PROF(a.prof, 26);
+            td_loss_finish(lrow, q0, q1, q2, AP, A, LP, a.gamma, inv_count, dq_s, a.stats_partial + ((size_t)b * RS + slice) * 8, t.lane);
+        DTQN_PROF_CLOCK(pclk[PK_LOSS_WAVE]);
+        if (t.tid < h2n4) st4(W5 + 4 * t.tid, h2);
+        for (int idx = t.tid + NT; idx < h2n4; idx += NT) st4(W5 + 4 * idx, ld4(W2h + 4 * idx));      // (more than 4 NT / D actions)
         __syncthreads();
-        DTQN_PROF(a.prof, 27);
+        DTQN_PROF_CLOCK(pclk[PK_LOSS_BARRIER]);
         if constexpr (WT) {
             for (int idx = t.tid; idx < LP * AP / 4; idx += NT) g_store4(gf(grec, net.go_dq, AP) + 4 * idx, ld4(dq_s + 4 * idx));   // AP = up4(A)
         } else {
@@ -224,40 +248,39 @@ __global__ __launch_bounds__(NW * 64) void dtqn_backward_kernel(BwdArgs a, Ahead
         }
     }
 
-    DTQN_PROF(a.prof, ps++);   // loss done
+    DTQN_PROF_CLOCK(pclk[PK_LOSS]);   // loss done
     // ---------------- B1: Q head backward ----------------
     // Memory discipline of this kernel: every global LOAD (weight fragments, saved activations) is
     // issued one stage before its use; every global STORE of a gradient tensor is a coalesced copy of
     // the LDS tile, issued at the start of the NEXT stage after the prefetched fragment has been
     // retired, so that no s_waitcnt ever sits behind a freshly issued store.
     {
-        const float* __restrict__ W2 = theta + net.off_head2_w;
         constexpr int C4 = D / 4;
 #pragma unroll
         for (int k4 = 0; k4 < TileRegs<NW, LP, D>::N; ++k4) {
             const int idx4 = t.tid + k4 * NT;
             if (idx4 < LP * C4) {
                 const int r = idx4 / C4, c0 = (idx4 - r * C4) * 4;
-                const float hv[4] = {trh.v[k4].x, trh.v[k4].y, trh.v[k4].z, trh.v[k4].w};
-                float g4[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float g = 0.f;
-                    if (hv[e] > 0.f)
-                        for (int c = 0; c < A; ++c) g = fmaf(dq_s[r * AP + c], W2[c * D + c0 + e], g);
-                    g4[e] = g;
+                // per element the same fmaf chain over the actions as ever, four elements side by side; hh <= 0 drops the result
+                float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
+                for (int c = 0; c < A; ++c) {
+                    const float d = dq_s[r * AP + c];
+                    const float4 w = ld4(W5 + c * D + c0);
+                    g.x = fmaf(d, w.x, g.x); g.y = fmaf(d, w.y, g.y); g.z = fmaf(d, w.z, g.z); g.w = fmaf(d, w.w, g.w);
                 }
-                st4(T2 + r * LDX + c0, make_float4(g4[0], g4[1], g4[2], g4[3]));
+                const float4 hv = trh.v[k4];
+                st4(T2 + r * LDX + c0, make_float4(hv.x > 0.f ? g.x : 0.f, hv.y > 0.f ? g.y : 0.f, hv.z > 0.f ? g.z : 0.f, hv.w > 0.f ? g.w : 0.f));
             }
         }
     }
+    DTQN_PROF_CLOCK(pclk[PK_HEAD2]);  // the elementwise pass is through: the head.2 operands were present
     __syncthreads();
     g_h1.retire();
     g_tile_store(T2, LDX, gf(grec, net.go_dhh, D), LP, D);
     if constexpr (SPLITS) g_h1.run(T2, LDX, t, red, [&](int r, int c, float v) { DX[r * LDX + c] = v; });      // (red: free until the first LayerNorm)
     else g_h1.run(T2, LDX, t, [&](int r, int c, float v) { DX[r * LDX + c] = v; });
     __syncthreads();
-    DTQN_PROF(a.prof, ps++);   // head done
+    DTQN_PROF_CLOCK(pclk[PK_HEAD]);   // head done
 
     // ---------------- layers, last to first ----------------
     for (int l = net.num_layers - 1; l >= 0; --l) {
@@ -283,22 +306,25 @@ __global__ __launch_bounds__(NW * 64) void dtqn_backward_kernel(BwdArgs a, Ahead
         const float* __restrict__ W2 = th + net.lo_f2_w;
         StageDyW<D, MT, pick_mg(NC / 16, MT, NW), NW, NC / 16> g_dh;      // dh = df W2[:, chunk]
         g_dh.prefetch(W2, 4 * D, t);
+        if (l == net.num_layers - 1) DTQN_PROF_CLOCK(pclk[PK_DH_PREFETCH]);
         // (mean, rstd) of both LayerNorms of this layer -> LDS (published by the next barrier); the previous layer's
         // reads of st_s ended behind a barrier, and the next layer's values go in flight now
         if (t.tid < 4 * LP) st_s[t.tid] = st_next;
         if (l > 0) st_next = st_fetch(l - 1);
+        if (l == net.num_layers - 1) DTQN_PROF_CLOCK(pclk[PK_STATS]);
 
         if (!ident) {   // x_out = LN2(s2): dL/ds2   (s2 was put in flight one stage ago)
-            if (l == net.num_layers - 1) DTQN_PROF(a.prof, 28);
+            if (l == net.num_layers - 1) DTQN_PROF_CLOCK(pclk[PK_S2_BEFORE]);
             tr.to_lds(T2, LDX, t);
-            if (l == net.num_layers - 1) DTQN_PROF(a.prof, 29);
+            if (l == net.num_layers - 1) DTQN_PROF_CLOCK(pclk[PK_S2_LDS]);
             __syncthreads();
-            if (l == net.num_layers - 1) DTQN_PROF(a.prof, 30);
+            if (l == net.num_layers - 1) DTQN_PROF_CLOCK(pclk[PK_S2_BARRIER]);
             layernorm_backward<D, NW, FUSE, PAD>(DX, T2, DX, false, LDX, LP, st_s + 2 * LP, th + net.lo_ln2_w, lsm + 2 * D, red, t, false, dreal);
-            if (l == net.num_layers - 1) DTQN_PROF(a.prof, 31);
+            if (l == net.num_layers - 1) DTQN_PROF_CLOCK(pclk[PK_LN2_BODY]);
             __syncthreads();
         }
-        DTQN_PROF(a.prof, ps++);   // LN2 bwd done
+        if (l == net.num_layers - 1) DTQN_PROF_CLOCK(pclk[PK_LN2]);   // LN2 bwd done
+        else DTQN_PROF(a.prof, ps++);
         tr.load(rf(lrec, net.al_s1, D), D, t);         // needed after the FFN: in flight during it
         // mlp gate.  res: s2 = x1 + relu(f)  ->  df = ds2 * [y2 > 0], the skip path keeps DX.
         // gru: DX <- dL/dx (skip path), T2 <- dL/dy, then the same ReLU mask.
@@ -808,6 +834,13 @@ __global__ __launch_bounds__(NW * 64) void dtqn_backward_kernel(BwdArgs a, Ahead
         DTQN_WAIT_VMEM();
         __syncthreads();
         fuse_arrive(a.fuse.counters, net.num_layers, t);
+    }
+    {   // the deferred marks: slots 0 .. 3 as the contiguous stage marks, the finer ones in 20 .. 23 and 24 .. 31 (25: free since the
+        // zero-fill barrier in front of the loss wave went; 16 .. 19 stay empty: tests/perf/stage_profile.py takes the marks up to
+        // the first empty slot for the contiguous ones)
+        constexpr int slot_of[PK_N] = {0, 24, 20, 26, 27, 1, 21, 2, 22, 23, 28, 29, 30, 31, 3};
+#pragma unroll
+        for (int k = 0; k < PK_N; ++k) DTQN_PROF_PUT(a.prof, slot_of[k], pclk[k]);
     }
 }
 

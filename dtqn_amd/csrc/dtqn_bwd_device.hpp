@@ -459,4 +459,81 @@ __device__ __forceinline__ void td_loss_wave(const float* q0, const float* q1, c
     }
 }
 
+// The same stage in two halves for the whole-sequence chain (dtqn_backward.hip), whose loss wave is the head of a serial chain: the one
+// round trip everything waits for is ISSUED first (td_loss_issue, in front of the kernel's prefetch batch) and consumed behind that batch
+// (td_loss_finish).  One row per lane (LPB <= 64).  Every load is unconditional: a lane whose row is outside the loss window
+// [L - history, L) reads row `stand_in` -- a row of the window that always exists -- and a select drops what it read, so the
+// number of loads in flight is the same for every lane and no wait behind them turns into "wait for everything".  Same arithmetic,
+// same first-maximum rule and same order of the wave reductions as td_loss_wave.
+constexpr int kLossQ4 = 2;        // float4s of a Q row taken in the first round trip (A <= 8: the whole row)
+struct TdLossRow {
+    bool live;
+    int at;
+    float rw;
+    int dn;
+    float4 v0[kLossQ4], v1[kLossQ4], v2[kLossQ4];
+};
+__device__ __forceinline__ void td_loss_issue(TdLossRow& w, const float* q0, const float* q1, const float* q2, int AP, int L, int LPB,
+                                              int history, int stand_in, const uint8_t* act, const float* rew, const uint8_t* don, int lane) {
+    w.live = lane < LPB && lane < L && lane >= L - history;
+    const int r = w.live ? lane : stand_in;
+    w.at = (int)act[r];
+    w.rw = rew[r];
+    w.dn = (int)don[r];
+#pragma unroll
+    for (int k = 0; k < kLossQ4; ++k) {
+        const int c = 4 * k < AP ? 4 * k : 0;      // AP = 4: the first float4 once more
+        w.v0[k] = ld4(q0 + r * AP + c);
+        w.v1[k] = ld4(q1 + r * AP + c);
+        w.v2[k] = ld4(q2 + r * AP + c);
+    }
+}
+//   dq: [LPB][AP] output (LDS): EVERY entry of the LPB rows is written here, zeros included
+__device__ __forceinline__ void td_loss_finish(const TdLossRow& w, const float* q0, const float* q1, const float* q2, int AP, int A, int LPB,
+                                               float gamma, float inv_count, float* dq, float* sp, int lane) {
+    float sq = 0.f, mnq = INFINITY, mxq = -INFINITY, sy = 0.f, mny = INFINITY, mxy = -INFINITY, se = 0.f;
+    int at = -1;
+    float g = 0.f;
+    if (w.live) {
+        at = w.at;
+        const float rw = w.rw;
+        const float dn = w.dn ? 1.f : 0.f;
+        float e0[4 * kLossQ4], e1[4 * kLossQ4], e2[4 * kLossQ4];
+#pragma unroll
+        for (int k = 0; k < kLossQ4; ++k) {
+            e0[4 * k] = w.v0[k].x; e0[4 * k + 1] = w.v0[k].y; e0[4 * k + 2] = w.v0[k].z; e0[4 * k + 3] = w.v0[k].w;
+            e1[4 * k] = w.v1[k].x; e1[4 * k + 1] = w.v1[k].y; e1[4 * k + 2] = w.v1[k].z; e1[4 * k + 3] = w.v1[k].w;
+            e2[4 * k] = w.v2[k].x; e2[4 * k + 1] = w.v2[k].y; e2[4 * k + 2] = w.v2[k].z; e2[4 * k + 3] = w.v2[k].w;
+        }
+        float q = 0.f, best = e1[0], qt = e2[0];
+#pragma unroll
+        for (int c = 0; c < 4 * kLossQ4; ++c) {    // torch.argmax: first maximal index
+            if (c < A) {
+                if (c == at) q = e0[c];
+                if (c > 0 && e1[c] > best) { best = e1[c]; qt = e2[c]; }
+            }
+        }
+        for (int c = 4 * kLossQ4; c < A; ++c) {    // wider action sets: the rest of the row, a second round trip
+            const float v0 = q0[lane * AP + c], v1 = q1[lane * AP + c], v2 = q2[lane * AP + c];
+            if (c == at) q = v0;
+            if (v1 > best) { best = v1; qt = v2; }
+        }
+        const float y = rw + (1.f - dn) * (qt * gamma);
+        const float diff = q - y;
+        g = 2.f * diff * inv_count;
+        sq += q; mnq = fminf(mnq, q); mxq = fmaxf(mxq, q);
+        sy += y; mny = fminf(mny, y); mxy = fmaxf(mxy, y);
+        se = fmaf(diff, diff, se);
+    }
+    if (lane < LPB) {
+        for (int c = 0; c < AP; c += 4)
+            st4(dq + lane * AP + c, make_float4(c == at ? g : 0.f, c + 1 == at ? g : 0.f, c + 2 == at ? g : 0.f, c + 3 == at ? g : 0.f));
+    }
+    sq = wave_sum(sq); sy = wave_sum(sy); se = wave_sum(se);
+    mnq = wave_min(mnq); mxq = wave_max(mxq); mny = wave_min(mny); mxy = wave_max(mxy);
+    if (lane == 0) {
+        sp[0] = se; sp[1] = sq; sp[2] = mxq; sp[3] = mnq; sp[4] = sy; sp[5] = mxy; sp[6] = mny; sp[7] = 0.f;
+    }
+}
+
 }  // namespace dtqn
