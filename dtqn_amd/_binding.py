@@ -122,6 +122,10 @@ def load_library(path: str) -> ctypes.CDLL:
         "dtqn_deval_step": [P(DtqnNet), vp, P(DtqnEval), u32, u32, i32, i32, i32, vp],
         "dtqn_deval_get_state": [P(DtqnNet), P(DtqnEval), vp, vp],
         "dtqn_deval_set_state": [P(DtqnNet), P(DtqnEval), vp, vp],
+        "dtqn_deval_begin_bag": [P(DtqnNet), P(DtqnEval), P(DtqnDevBag), u32, i32, vp],
+        "dtqn_deval_step_bag": [P(DtqnNet), vp, P(DtqnEval), P(DtqnDevBag), u32, u32, i32, i32, i32, i32, vp],
+        "dtqn_bag_candidates_workspace_floats": [P(DtqnNet), i32, i32],
+        "dtqn_forward_bag_candidates": [P(DtqnNet), vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp],
         "dtqn_forward_tiled_strided": [P(DtqnNet), vp, vp, vp, i32, i32, i32, vp, vp, vp],
         "dtqn_forward_bag": [P(DtqnNet), vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, u32, u32, vp],
         "dtqn_forward": [P(DtqnNet), vp, vp, vp, i32, i32, vp, vp],

@@ -67,7 +67,8 @@ class DeviceEnvs:
         if getattr(agent, "image", None) is not None:
             raise NotImplementedError(f"device-resident {what}: image networks are not covered (use {self.FLAG})")
         if agent.bag.size > 0 and not self.BAGS:
-            raise NotImplementedError(f"device-resident {what}: bag networks are not covered (use {self.FLAG})")
+            raise NotImplementedError(f"device-resident {what}: bag networks are not covered by this class (use {self.FLAG}, or the bag "
+                                      f"classes: --device-envs with --bag-size / --device-bag-eval-envs)")
         if agent.dp is not None or ddp.is_distributed():
             raise NotImplementedError(f"device-resident {what}: data-parallel runs are not covered")
         self._refuse(agent)

@@ -343,6 +343,50 @@ extern "C" int dtqn_deval_step(const DtqnNet* net, const float* theta, const Dtq
     return dtqn::deval_step_launch(net, ev, key, step, cur, n_max, episodes, (hipStream_t)stream);
 }
 
+// Device-resident evaluation of a bag network: dtqn_deval_begin / _step with one bag per environment (dtqn_devbag.hip) -- up to five
+// launches per step, nothing between.  DTQN_ERR_CONFIG for a network without a bag.
+static int deval_bag_check(const DtqnNet* net, const DtqnEval* ev, const DtqnDevBag* bag) {
+    if (!bag) return DTQN_ERR_ARG;
+    const int rc = dtqn::deval_check_bags(net, ev);
+    return rc != DTQN_OK ? rc : dtqn::devbag_check_eval(net, ev, bag);
+}
+
+extern "C" int dtqn_deval_begin_bag(const DtqnNet* net, const DtqnEval* ev, const DtqnDevBag* bag, uint32_t key, int episodes, void* stream) {
+    int rc = deval_bag_check(net, ev, bag);
+    if (rc != DTQN_OK) return rc;
+    if (episodes < 0 || episodes > ev->max_episodes) return DTQN_ERR_ARG;
+    if ((rc = dtqn::deval_begin_launch(net, ev, key, episodes, (hipStream_t)stream)) != DTQN_OK) return rc;
+    return dtqn::devbag_stage_launch_eval(net, ev, bag, 0, 1, 0, (hipStream_t)stream);
+}
+
+extern "C" int dtqn_deval_step_bag(const DtqnNet* net, const float* theta, const DtqnEval* ev, const DtqnDevBag* bag, uint32_t key, uint32_t step,
+                                   int cur, int n_max, int episodes, int may_choose, void* stream) {
+    int rc = deval_bag_check(net, ev, bag);
+    if (rc != DTQN_OK) return rc;
+    if (cur != 0 && cur != 1) return DTQN_ERR_ARG;
+    if (episodes < 0 || episodes > ev->max_episodes) return DTQN_ERR_ARG;
+    if (!theta || !ev->q_dev) return DTQN_ERR_ARG;
+    const int N = ev->n_envs, L = net->ctx_len;
+    if (n_max < 1 || n_max > L) return DTQN_ERR_ARG;                            // dtqn.py:170-173
+    hipStream_t s = (hipStream_t)stream;
+    const dtqn::DevalLayout l = dtqn::deval_layout(net, ev);
+    const dtqn::DevBagViews v = dtqn::devbag_views(net, bag);
+    const ActorBlock b = actor_block(net, static_cast<uint8_t*>(ev->state) + l.off[8 + cur], N);
+    rc = dtqn::tiled_forward_bag_resident(net, theta, b.obs, b.actions, v.bag_obs, v.bag_act, N, n_max, L, ev->q_dev, bag->workspace, 0, 0u, 0u, s,
+                                          b.lens, nullptr, nullptr);
+    if (rc != DTQN_OK) return rc;
+    if ((rc = dtqn::deval_step_launch(net, ev, key, step, cur, n_max, episodes, s)) != DTQN_OK) return rc;
+    if ((rc = dtqn::devbag_stage_launch_eval(net, ev, bag, cur, 0, may_choose ? 1 : 0, s)) != DTQN_OK) return rc;
+    if (!may_choose) return DTQN_OK;
+    // the K + 1 candidate bags of environment i on its one context after the transition: the layers once per environment, on the full L
+    // rows of the block the step wrote
+    const ActorBlock out = actor_block(net, static_cast<uint8_t*>(ev->state) + l.off[8 + (cur ^ 1)], N);
+    rc = dtqn::tiled_forward_bag_candidates(net, theta, out.obs, out.actions, v.cand_obs, v.cand_act, N, net->bag_size + 1, L, bag->q_cand,
+                                            bag->workspace, s);
+    if (rc != DTQN_OK) return rc;
+    return dtqn::devbag_select_launch(net, bag, s);
+}
+
 // The differentiable forward without dropout (the function the no-grad forward computes): the _drop entry points with the masks off.
 extern "C" int dtqn_forward_train(const DtqnNet* net, const float* theta, const float* obs, const uint8_t* actions, const float* bag_obs,
                                   const uint8_t* bag_actions, int batch, int n, float* q_out, float* workspace, void* stream) {

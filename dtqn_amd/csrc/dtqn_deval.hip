@@ -173,10 +173,13 @@ static DevalArgs deval_args(const DtqnNet* net, const DtqnEval* ev, uint32_t key
     return a;
 }
 
-int deval_check(const DtqnNet* net, const DtqnEval* ev) {
+static int deval_check_net(const DtqnNet* net, const DtqnEval* ev, int bags) {
     if (!net || !ev || !ev->state || !ev->status_host || ev->n_envs < 1 || ev->max_episodes < 1) return DTQN_ERR_ARG;
-    return devenv_check(net, ev);
+    return devenv_check(net, ev, bags);
 }
+int deval_check(const DtqnNet* net, const DtqnEval* ev) { return deval_check_net(net, ev, 0); }
+// The twin that admits a bag network: the bag path's entry points (dtqn_api.cpp) and get_state / set_state, which launch no forward.
+int deval_check_bags(const DtqnNet* net, const DtqnEval* ev) { return deval_check_net(net, ev, 1); }
 
 int deval_begin_launch(const DtqnNet* net, const DtqnEval* ev, uint32_t key, int episodes, hipStream_t stream) {
     return devenv_launch(dtqn_deval_begin_kernel, deval_args(net, ev, key, 1, episodes), stream);         // a begin writes the `out` block: block 0
@@ -211,10 +214,10 @@ extern "C" int dtqn_deval_begin(const DtqnNet* net, const DtqnEval* ev, uint32_t
 }
 
 extern "C" int dtqn_deval_get_state(const DtqnNet* net, const DtqnEval* ev, void* host, void* stream) {
-    if (!host || deval_check(net, ev) != DTQN_OK) return DTQN_ERR_ARG;
+    if (!host || deval_check_bags(net, ev) != DTQN_OK) return DTQN_ERR_ARG;
     return devenv_copy_state(host, ev->state, deval_layout(net, ev).bytes, hipMemcpyDeviceToHost, stream);
 }
 extern "C" int dtqn_deval_set_state(const DtqnNet* net, const DtqnEval* ev, const void* host, void* stream) {
-    if (!host || deval_check(net, ev) != DTQN_OK) return DTQN_ERR_ARG;
+    if (!host || deval_check_bags(net, ev) != DTQN_OK) return DTQN_ERR_ARG;
     return devenv_copy_state(ev->state, host, deval_layout(net, ev).bytes, hipMemcpyHostToDevice, stream);
 }

@@ -34,6 +34,8 @@ inline DevalLayout deval_layout(const DtqnNet* net, const DtqnEval* ev) {
 
 // DTQN_OK when the descriptor and the network fit the kernels (flat f32 observations of the environment's width, ...)
 int deval_check(const DtqnNet* net, const DtqnEval* ev);
+// ... and the same check for the callers that admit a bag network (dtqn_devbag.hpp)
+int deval_check_bags(const DtqnNet* net, const DtqnEval* ev);
 int deval_begin_launch(const DtqnNet* net, const DtqnEval* ev, uint32_t key, int episodes, hipStream_t stream);
 // Q of the last live rows: q_last [N][A] (whole-sequence networks) or q_dev with n_max rows per sequence (row-block ones)
 int deval_step_launch(const DtqnNet* net, const DtqnEval* ev, uint32_t key, uint32_t step, int cur, int n_max, int episodes, hipStream_t stream);

@@ -14,6 +14,7 @@
 //                              (torch.argmax) becomes the bag.
 // Plain vector stores only; no thread keeps an indexed private array.
 #include "dtqn_devbag.hpp"
+#include "dtqn_deval.hpp"
 #include "dtqn_devenv.hpp"
 #include "dtqn_rollout.hpp"
 
@@ -184,14 +185,22 @@ static DevBagArgs devbag_args(const DtqnNet* net, const DtqnDevBag* bag) {
     return a;
 }
 
-int devbag_check(const DtqnNet* net, const DtqnRollout* ro, const DtqnDevBag* bag) {
-    if (!net || !ro || !bag) return DTQN_ERR_ARG;
-    if (net->bag_size < 1 || !net->tiled || net->dropout > 0.f || net->bag_size + 1 > DTQN_DEVBAG_MAX_CANDIDATES) return DTQN_ERR_CONFIG;
-    if (!bag->state || !bag->q_cand || !bag->workspace || bag->n_envs < 1 || bag->n_envs != ro->n_envs) return DTQN_ERR_ARG;
+// The descriptor against the network and the environment count of the state it rides on.
+static int devbag_check_desc(const DtqnNet* net, int n_envs, const DtqnDevBag* bag, bool dropout_ok) {
+    if (net->bag_size < 1 || !net->tiled || (net->dropout > 0.f && !dropout_ok) || net->bag_size + 1 > DTQN_DEVBAG_MAX_CANDIDATES) return DTQN_ERR_CONFIG;
+    if (!bag->state || !bag->q_cand || !bag->workspace || bag->n_envs < 1 || bag->n_envs != n_envs) return DTQN_ERR_ARG;
     if (!(bag->obs_mask == bag->obs_mask)) return DTQN_ERR_ARG;
     // q_cand's floats and the state's offsets stay inside an int
     if ((long long)bag->n_envs * (net->bag_size + 1) * net->ctx_len * net->num_actions > 0x7fffffffLL) return DTQN_ERR_ARG;
     return devbag_layout(net, bag).bytes > 0x7fffffffull ? DTQN_ERR_ARG : DTQN_OK;
+}
+int devbag_check(const DtqnNet* net, const DtqnRollout* ro, const DtqnDevBag* bag) {
+    if (!net || !ro || !bag) return DTQN_ERR_ARG;
+    return devbag_check_desc(net, ro->n_envs, bag, false);
+}
+int devbag_check_eval(const DtqnNet* net, const DtqnEval* ev, const DtqnDevBag* bag) {
+    if (!net || !ev || !bag) return DTQN_ERR_ARG;
+    return devbag_check_desc(net, ev->n_envs, bag, true);
 }
 
 DevBagViews devbag_views(const DtqnNet* net, const DtqnDevBag* bag) {
@@ -206,6 +215,19 @@ int devbag_stage_launch(const DtqnNet* net, const DtqnReplay* rp, const DtqnRoll
     uint8_t* base = static_cast<uint8_t*>(ro->state);
     const ActorBlock in = actor_block(net, base + l.off[6 + (cur & 1)], ro->n_envs);
     a.last = reinterpret_cast<const int32_t*>(base + l.off[5]);
+    a.elapsed = reinterpret_cast<const int32_t*>(base + l.off[3]);
+    a.obs_in = in.obs;
+    a.reset_all = reset_all; a.may_choose = may_choose;
+    return devenv_launch(dtqn_devbag_stage_kernel, a, stream);
+}
+
+int devbag_stage_launch_eval(const DtqnNet* net, const DtqnEval* ev, const DtqnDevBag* bag, int cur, int reset_all, int may_choose,
+                             hipStream_t stream) {
+    DevBagArgs a = devbag_args(net, bag);
+    const DevalLayout l = deval_layout(net, ev);
+    uint8_t* base = static_cast<uint8_t*>(ev->state);
+    const ActorBlock in = actor_block(net, base + l.off[8 + (cur & 1)], ev->n_envs);
+    a.last = reinterpret_cast<const int32_t*>(base + l.off[6]);
     a.elapsed = reinterpret_cast<const int32_t*>(base + l.off[3]);
     a.obs_in = in.obs;
     a.reset_all = reset_all; a.may_choose = may_choose;

@@ -28,6 +28,8 @@ inline DevBagLayout devbag_layout(const DtqnNet* net, const DtqnDevBag* bag) {
 
 // DTQN_OK when the bag descriptor fits the network and the rollout it rides on; DTQN_ERR_CONFIG: no bag, dropout, too many candidates.
 int devbag_check(const DtqnNet* net, const DtqnRollout* ro, const DtqnDevBag* bag);
+// The same for the bags of the device-resident evaluation, which admits dropout: it never runs train mode.
+int devbag_check_eval(const DtqnNet* net, const DtqnEval* ev, const DtqnDevBag* bag);
 // The sections the forwards read: the bags (actor forward), the candidates and their sequence -> context index table (candidate forward).
 struct DevBagViews {
     const float *bag_obs, *cand_obs;
@@ -39,6 +41,9 @@ DevBagViews devbag_views(const DtqnNet* net, const DtqnDevBag* bag);
 // the rollout's step kernel has run on block `cur` (it reads `last`, `elapsed` and row 0 of block `cur` out of the rollout's state).
 int devbag_stage_launch(const DtqnNet* net, const DtqnReplay* rp, const DtqnRollout* ro, const DtqnDevBag* bag, int cur, int reset_all,
                         int may_choose, hipStream_t stream);
+// The same kernel behind the evaluation's step kernel: `last`, `elapsed` and row 0 of block `cur` out of the evaluation's state.
+int devbag_stage_launch_eval(const DtqnNet* net, const DtqnEval* ev, const DtqnDevBag* bag, int cur, int reset_all, int may_choose,
+                             hipStream_t stream);
 int devbag_select_launch(const DtqnNet* net, const DtqnDevBag* bag, hipStream_t stream);
 
 // dtqn_tiled.hip: the row-block forward of a bag network on resident arrays.  lens: ragged prefixes or nullptr (n rows each); seq_src /
@@ -47,5 +52,11 @@ int tiled_forward_bag_resident(const DtqnNet* net, const float* theta, const flo
                                const uint8_t* bag_actions, int batch, int n, int in_rows, float* q_out, float* workspace, int train_mode,
                                uint32_t drop_seed, uint32_t drop_step, hipStream_t stream, const int32_t* lens, const int32_t* seq_src,
                                const int32_t* seq_start);
+
+// The candidate forward on a shared trunk: eval-mode Q of n_ctx whole contexts under n_cand candidate bags each (cand_obs
+// [n_ctx][n_cand][K][O], cand_act [n_ctx][n_cand][K]) -> q_out [n_ctx][n_cand][L][A]; the layers run once per context.  workspace:
+// dtqn_bag_candidates_workspace_floats(net, n_ctx, n_cand) floats.
+int tiled_forward_bag_candidates(const DtqnNet* net, const float* theta, const float* obs, const uint8_t* actions, const float* cand_obs,
+                                 const uint8_t* cand_act, int n_ctx, int n_cand, int in_rows, float* q_out, float* workspace, hipStream_t stream);
 
 }  // namespace dtqn

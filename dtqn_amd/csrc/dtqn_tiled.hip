@@ -3518,6 +3518,20 @@ __global__ __launch_bounds__(TNT) void tl_copy_kernel(TlCopyArgs a) {
         st4(frow(a.dst, s, row0 + r) + c, ld4(frow(a.src, s, row0 + r) + c));
     }
 }
+// dst[s][rows][cols] = src[s / div][rows][cols]: the working memory of one context -> every candidate sequence that shares it
+// (tiled_forward_bag_candidates); src and dst are different records
+struct TlBcastArgs {
+    Fld src, dst;
+    int cols, rpb, div;
+};
+__global__ __launch_bounds__(TNT) void tl_bcast_kernel(TlBcastArgs a) {
+    const int s = (int)blockIdx.x / a.rpb, row0 = ((int)blockIdx.x % a.rpb) * TROWS;
+    const int c4 = a.cols / 4;
+    for (int idx = (int)threadIdx.x; idx < TROWS * c4; idx += TNT) {
+        const int r = idx / c4, c = (idx - r * c4) * 4;
+        st4(frow(a.dst, s, row0 + r) + c, ld4(frow(a.src, s / a.div, row0 + r) + c));
+    }
+}
 
 // ---- launch helpers --------------------------------------------------------------------------------------------------------
 // DTQN_TL_TRACE=1 (tests): one line per launch on stderr, so a test can tell WHICH kernels an update went through and on what grid
@@ -3946,11 +3960,16 @@ static TlFwdPlan tl_fwd_plan(const DtqnNet& net, const EmbedSrc& src, int S, int
     return p;
 }
 
+// The two parts of a forward: the trunk (embedding and every layer, up to the working memory) and the tail (a bag network's persistent
+// memory, then the head).  Every caller runs both but the candidate forward on a shared trunk (tiled_forward_bag_candidates).
+enum { TL_FWD_TRUNK = 1, TL_FWD_TAIL = 2, TL_FWD_ALL = 3 };
+
 // All S sequences through the network.  theta_a serves sequences [0, split), theta_b the rest.
 template <int D>
 static int forward_records(const DtqnNet& net, const float* theta_a, const float* theta_b, int split, const EmbedSrc& src,
                            int S, int n, float* rec, bool training, float* q_out, long long q_seq_stride, int q_row_stride,
-                           hipStream_t stream, const TlDrop& drop, const float* pk_a = nullptr, const float* pk_b = nullptr) {
+                           hipStream_t stream, const TlDrop& drop, const float* pk_a = nullptr, const float* pk_b = nullptr,
+                           int parts = TL_FWD_ALL) {
     // fragment-major weight copies of the two parameter sets (dtqn_wpack.hpp; nullptr: the kernels read the parameter layout)
     const WPackPlan wplan = (pk_a != nullptr && pk_b != nullptr) ? wpack_plan(net) : WPackPlan{};
     const int lpb = net.lp, H = net.num_heads, HD = net.head_dim, rpb = lpb / TROWS;
@@ -3961,7 +3980,8 @@ static int forward_records(const DtqnNet& net, const float* theta_a, const float
     int rc;
     auto F = [&](int off, int ld) { return fld(rec, rm.stride, off, ld); };
     auto L0 = [&](int l) { return net.ao_layer0 + l * rm.layer_stride; };
-    {
+    const bool trunk = (parts & TL_FWD_TRUNK) != 0;
+    if (trunk) {
         TlEmbedArgs e;
         e.net = net; e.theta_a = theta_a; e.theta_b = theta_b; e.split = split;
         e.obs = src.obs; e.actions = src.actions; e.obs_ep_stride = src.obs_ep_stride; e.act_ep_stride = src.act_ep_stride;
@@ -4040,7 +4060,7 @@ static int forward_records(const DtqnNet& net, const float* theta_a, const float
     const bool padded = net.d_real > 0;           // (width-padded networks keep their LayerNorms in launches of their own)
     bool head_done = false;
     int qkv_done_for = qkv0_done ? 0 : -1;
-    for (int l = 0; l < net.num_layers; ++l) {
+    for (int l = 0; trunk && l < net.num_layers; ++l) {
         const int tb = net.off_layer0 + l * net.layer_stride, ab = L0(l);
         const bool last = l + 1 == net.num_layers;
         const Fld u1 = F(ab + net.al_u1, D), s1 = F(ab + net.al_s1, D), u2 = F(ab + net.al_u2, D), s2 = F(ab + net.al_s2, D);
@@ -4175,6 +4195,7 @@ static int forward_records(const DtqnNet& net, const float* theta_a, const float
             if ((rc = lnorm(s2, nxt, st2, tb + net.lo_ln2_w, tb + net.lo_ln2_b)) != DTQN_OK) return rc;
         }
     }
+    if (!(parts & TL_FWD_TAIL)) return DTQN_OK;      // (the working memory is in xcat, or with identity layers in s2 of the last layer)
     const Fld xf = ident ? F(L0(net.num_layers - 1) + net.al_s2, D) : F(rm.xf, D);
     if (net.bag_size > 0) {
         // ---- persistent memory (dtqn.py:201-214): embed the bag entries, attend from the working memory over them, and feed
@@ -4606,6 +4627,71 @@ int tiled_forward_bag_resident(const DtqnNet* net, const float* theta, const flo
                               drop_step, lens, nullptr, seq_src, seq_start);
 }
 }  // namespace dtqn
+
+// ---- candidate forward on a shared trunk -------------------------------------------------------------------------------------------
+// The K + 1 candidate bags of an environment share its one context, and the bag enters the network only behind the layers
+// (dtqn.py:195-214): the trunk runs once per context, the tail once per (context, candidate).  Workspace: [n_ctx] records of the trunk |
+// [n_ctx n_cand] records of the tail, both of the inference record's size, so that the tail addresses its fields as in every other forward.
+extern "C" int dtqn_bag_candidates_workspace_floats(const DtqnNet* net, int n_ctx, int n_cand) {
+    if (!net || n_ctx < 1 || n_cand < 1 || !net->tiled || net->bag_size < 1) return 0;
+    const long long fl = ((long long)n_ctx + (long long)n_ctx * n_cand) * rec_map(*net, false).stride;
+    return fl < 0x7fffffffLL ? (int)fl : 0;
+}
+
+template <int D>
+static int forward_bag_candidates(const DtqnNet& net, const float* theta, const EmbedSrc& ctx_src, const EmbedSrc& cand_src, int n_ctx, int n_cand,
+                                  float* q_out, float* workspace, hipStream_t stream) {
+    const int L = net.ctx_len, S = n_ctx * n_cand, rpb = net.lp / TROWS;
+    const RecMap rm = rec_map(net, false);
+    const long long qs = (long long)L * net.num_actions;
+    float* rec_ctx = workspace;
+    float* rec_cand = workspace + (size_t)n_ctx * rm.stride;
+    int rc = forward_records<D>(net, theta, theta, n_ctx, ctx_src, n_ctx, L, rec_ctx, false, nullptr, qs, net.num_actions, stream,
+                                tl_drop_make(net, 0u, 0u, nullptr, n_ctx, 0), nullptr, nullptr, TL_FWD_TRUNK);
+    if (rc != DTQN_OK) return rc;
+    // the working memory of context s / n_cand -> where the tail of sequence s reads it: the left half of xcat; identity layers: s2 of the
+    // (one, reused) layer region, which the tail's tl_copy_kernel branch then copies into xcat
+    TlBcastArgs b;
+    const int off = net.identity != 0 ? net.ao_layer0 + net.al_s2 : rm.xcat, ld = net.identity != 0 ? D : 2 * D;
+    b.src = fld(rec_ctx, rm.stride, off, ld); b.dst = fld(rec_cand, rm.stride, off, ld);
+    b.cols = D; b.rpb = rpb; b.div = n_cand;
+    TL_LAUNCH(tl_bcast_kernel, dim3(S * rpb), dim3(TNT), 0, stream, b);
+    return forward_records<D>(net, theta, theta, S, cand_src, S, L, rec_cand, false, q_out, qs, net.num_actions, stream,
+                              tl_drop_make(net, 0u, 0u, nullptr, S, 0), nullptr, nullptr, TL_FWD_TAIL);
+}
+
+namespace dtqn {
+// Eval-mode Q of n_ctx contexts (whole: ctx_len rows each, `in_rows` rows apart in obs / actions) under n_cand candidate bags each
+// (cand_obs [n_ctx][n_cand][K][O], cand_act [n_ctx][n_cand][K]) -> q_out [n_ctx][n_cand][L][A].
+int tiled_forward_bag_candidates(const DtqnNet* net, const float* theta, const float* obs, const uint8_t* actions, const float* cand_obs,
+                                 const uint8_t* cand_act, int n_ctx, int n_cand, int in_rows, float* q_out, float* workspace, hipStream_t stream) {
+    if (!net || !theta || !obs || !cand_obs || !q_out || !workspace || n_ctx < 1 || n_cand < 1) return DTQN_ERR_ARG;
+    if (net->bag_size < 1 || !net->tiled || net->img_c > 0) return DTQN_ERR_CONFIG;
+    if (in_rows < net->ctx_len || (net->action_dim > 0 && (!actions || !cand_act))) return DTQN_ERR_ARG;
+    if (dtqn_bag_candidates_workspace_floats(net, n_ctx, n_cand) <= 0) return DTQN_ERR_ARG;
+    const int S = n_ctx * n_cand;
+    EmbedSrc ctx_src;
+    ctx_src.obs = obs; ctx_src.actions = actions;
+    ctx_src.obs_ep_stride = (long long)in_rows * net->obs_dim; ctx_src.act_ep_stride = in_rows;
+    ctx_src.ep_idx = nullptr; ctx_src.start = nullptr; ctx_src.batch = n_ctx;
+    EmbedSrc cand_src = ctx_src;                         // (the tail embeds the bags alone)
+    cand_src.batch = S;
+    cand_src.bag_obs = cand_obs; cand_src.bag_actions = cand_act; cand_src.bag_batch = S;
+    switch (net->d_model) {
+        case 64: return forward_bag_candidates<64>(*net, theta, ctx_src, cand_src, n_ctx, n_cand, q_out, workspace, stream);
+        case 128: return forward_bag_candidates<128>(*net, theta, ctx_src, cand_src, n_ctx, n_cand, q_out, workspace, stream);
+        case 256: return forward_bag_candidates<256>(*net, theta, ctx_src, cand_src, n_ctx, n_cand, q_out, workspace, stream);
+        default: return DTQN_ERR_CONFIG;
+    }
+}
+}  // namespace dtqn
+
+extern "C" int dtqn_forward_bag_candidates(const DtqnNet* net, const float* theta, const float* obs, const uint8_t* actions, const float* cand_obs,
+                                           const uint8_t* cand_act, int n_ctx, int n_cand, int in_rows, float* q_out, float* workspace,
+                                           void* stream) {
+    return dtqn::tiled_forward_bag_candidates(net, theta, obs, actions, cand_obs, cand_act, n_ctx, n_cand, in_rows, q_out, workspace,
+                                              (hipStream_t)stream);
+}
 
 // in_rows: rows per sequence in the obs / actions arrays (>= n; the batched actor packs whole contexts)
 extern "C" int dtqn_forward_tiled_strided(const DtqnNet* net, const float* theta, const float* obs, const uint8_t* actions,

@@ -469,8 +469,9 @@ int dtqn_rollout_set_state(const DtqnNet* net, const DtqnReplay* rp, const DtqnR
  * environment in a device allocation of its own, next to the DtqnRollout state.  The actor forward takes the bags; what a full
  * context evicts is appended to its environment's bag, and a full bag keeps the best of its K + 1 candidate contents by the policy
  * network's mean-over-time max-Q (dtqn/agents/dtqn.py:125-157) -- a batched forward over N (K + 1) sequences and a reduction, nothing
- * read back.  dtqn_rollout_reset / _step / dtqn_deval_* keep refusing bag networks (DTQN_ERR_CONFIG); dtqn_rollout_commit / _get_state /
- * _set_state serve both.  K = net->bag_size, N = n_envs, O = obs_dim, L = ctx_len, A = num_actions.
+ * read back.  dtqn_rollout_reset / _step / dtqn_deval_begin / _step keep refusing bag networks (DTQN_ERR_CONFIG); dtqn_rollout_commit and
+ * the _get_state / _set_state of both serve both.  The same descriptor and state carry the bags of the device-resident evaluation
+ * (dtqn_deval_begin_bag / dtqn_deval_step_bag below), with n_envs that of the DtqnEval.  K = net->bag_size, N = n_envs, O = obs_dim, L = ctx_len, A = num_actions.
  * state layout (byte offsets from dtqn_devbag_state_bytes, every section 16-byte aligned):
  *   [0] bag_obs   f32[N][K][O]        [1] bag_act  u8[N][K]        [2] bag_pos  i32[N]   entries in the bag (0 .. K)
  *   [3] cand_obs  f32[N][K+1][K][O]   [4] cand_act u8[N][K+1][K]   candidate c < K: entry c replaced by the evicted pair; candidate K: the bag
@@ -488,8 +489,9 @@ int dtqn_rollout_set_state(const DtqnNet* net, const DtqnReplay* rp, const DtqnR
 typedef struct DtqnDevBag {
     void* state;                      /* device, dtqn_devbag_state_bytes() bytes, zeroed once by the caller */
     float* q_cand;                    /* device [N (K+1)][L][A]: Q of the candidate forward */
-    float* workspace;                 /* dtqn_forward_workspace_floats(net, N (K+1)) floats; the actor forward may share it */
-    int32_t n_envs;                   /* N: equals DtqnRollout::n_envs */
+    float* workspace;                 /* rollout: dtqn_forward_workspace_floats(net, N (K+1)) floats; evaluation:
+                                         dtqn_bag_candidates_workspace_floats(net, N, K+1).  The actor forward may share it */
+    int32_t n_envs;                   /* N: equals DtqnRollout::n_envs / DtqnEval::n_envs */
     float obs_mask;                   /* padding value of an empty bag entry (Bag.make_empty_bag) */
 } DtqnDevBag;
 /* Bytes of DtqnDevBag::state; offsets (may be NULL): int32[DTQN_DEVBAG_OFFSETS] byte offsets of the sections above.  < 0: bad arguments. */
@@ -565,6 +567,21 @@ int dtqn_deval_step(const DtqnNet* net, const float* theta, const DtqnEval* ev, 
 /* Copy the whole state to / from host memory (asynchronous on `stream`; pinned memory keeps it so). */
 int dtqn_deval_get_state(const DtqnNet* net, const DtqnEval* ev, void* host, void* stream);
 int dtqn_deval_set_state(const DtqnNet* net, const DtqnEval* ev, const void* host, void* stream);
+/* ------------------------------------------------------------------------------------------
+ * Device-resident greedy evaluation of a bag network (DESIGN.md "Device-resident evaluation of a bag network"): the evaluation above
+ * with one persistent-memory bag per environment, a DtqnDevBag whose n_envs is ev->n_envs.  dtqn_deval_begin / dtqn_deval_step keep
+ * returning DTQN_ERR_CONFIG for a bag network; these return it for a network without one.  Dropout > 0 is admitted: an evaluation
+ * never runs train mode.
+ * ------------------------------------------------------------------------------------------ */
+/* dtqn_deval_begin, plus: every bag cleared (obs_mask / action 0 / pos 0), the candidate slots initialised to the cleared bag. */
+int dtqn_deval_begin_bag(const DtqnNet* net, const DtqnEval* ev, const DtqnDevBag* bag, uint32_t key, int episodes, void* stream);
+/* One vector step, all on `stream`, nothing between: the eval-mode forward on block `cur` with the bags, dtqn_deval_step's step kernel,
+ * dtqn_devbag_stage_kernel on the evaluation's state (episode finished: bag cleared, whatever the next episode's `elapsed` says; idle
+ * environment: nothing; window slid: the evicted pair appended, or with a full bag the K + 1 candidates written), and with
+ * may_choose != 0 dtqn_forward_bag_candidates on the L rows of block cur ^ 1 and dtqn_devbag_select_kernel.  may_choose as
+ * dtqn_rollout_step_bag's, counted in vector steps since the begin; every other argument as dtqn_deval_step. */
+int dtqn_deval_step_bag(const DtqnNet* net, const float* theta, const DtqnEval* ev, const DtqnDevBag* bag, uint32_t key, uint32_t step, int cur,
+                        int n_max, int episodes, int may_choose, void* stream);
 /* DTQN.forward with the bag arguments (dtqn.py:158-218 incl. :201-214): bag_obs [B][bag_size][O] f32, bag_actions [B][bag_size] u8
  * (NULL when action_dim == 0).  Row-block tiled path; workspace as dtqn_forward_tiled.
  * train_mode != 0 with net->dropout > 0: a train-mode forward (the reference's policy network stays in train mode while the agent
@@ -572,6 +589,15 @@ int dtqn_deval_set_state(const DtqnNet* net, const DtqnEval* ev, const void* hos
 int dtqn_forward_bag(const DtqnNet* net, const float* theta, const float* obs, const uint8_t* actions, const float* bag_obs,
                      const uint8_t* bag_actions, int batch, int n, float* q_out, float* workspace, int train_mode,
                      uint32_t dropout_seed, uint32_t dropout_step, void* stream);
+/* Candidate scoring on a shared trunk: eval-mode Q of n_ctx WHOLE contexts (ctx_len rows each, `in_rows` >= ctx_len rows apart in obs /
+ * actions) under n_cand candidate bags each -- cand_obs [n_ctx][n_cand][bag_size][O] f32, cand_act [n_ctx][n_cand][bag_size] u8 (NULL
+ * when action_dim == 0) -> q_out [n_ctx][n_cand][ctx_len][num_actions].  The bag enters the network behind the transformer layers
+ * (dtqn.py:195-214), so embedding and layers run once per context and only the bag branch and the head per (context, candidate): the
+ * function dtqn_forward_bag computes on the n_ctx n_cand tiled inputs.  workspace: dtqn_bag_candidates_workspace_floats floats (0:
+ * the shape is not covered: no bag, not a row-block network, or too large). */
+int dtqn_bag_candidates_workspace_floats(const DtqnNet* net, int n_ctx, int n_cand);
+int dtqn_forward_bag_candidates(const DtqnNet* net, const float* theta, const float* obs, const uint8_t* actions, const float* cand_obs,
+                                const uint8_t* cand_act, int n_ctx, int n_cand, int in_rows, float* q_out, float* workspace, void* stream);
 /* dtqn_forward_tiled with `in_rows` (>= n) rows per sequence in the obs / actions arrays. */
 int dtqn_forward_tiled_strided(const DtqnNet* net, const float* theta, const float* obs, const uint8_t* actions, int batch, int n,
                                int in_rows, float* q_out, float* workspace, void* stream);

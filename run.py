@@ -79,8 +79,8 @@ def get_args(argv: Optional[Sequence[str]] = None):
                         "tabular POMDP environments on the GPU behind the batched actor forward, prepopulation included; the loop is that of "
                         "--num-envs (N updates per vector step).  Needs --sampler device; 0 = off.  With --bag-size K > 0 the bags live on "
                         "the GPU too (dtqn_amd.agents.device_bag.DeviceBagVectorActor: appended, and chosen among K + 1 candidates by a "
-                        "batched forward, with nothing read back); evaluation of a bag run stays on the host (--eval-envs), "
-                        "--device-eval-envs refuses it")
+                        "batched forward, with nothing read back); the device-resident evaluation of a bag run is "
+                        "--device-bag-eval-envs, --device-eval-envs refuses it")
     p.add_argument("--overlap", action="store_true",
                    help="pipeline the actor forward of step t+1 with TD update t+1 on two HIP streams (same policy-vs-action "
                         "semantics; an episode that ends at step t becomes sampleable one update later)")
@@ -90,7 +90,12 @@ def get_args(argv: Optional[Sequence[str]] = None):
     p.add_argument("--device-eval-envs", type=int, default=0,
                    help="device-resident greedy evaluation (dtqn_amd.agents.device_eval.DeviceEvaluator): N > 0 plays the evaluation "
                         "episodes of CarFlag / Memory / tabular POMDP domains N at a time on the GPU, with no host round trip per step; with or without "
-                        "--device-envs, not with --eval-envs > 1; 0 = off")
+                        "--device-envs, not with --eval-envs > 1; 0 = off.  A bag network (--bag-size K > 0) is refused: "
+                        "--device-bag-eval-envs")
+    p.add_argument("--device-bag-eval-envs", type=int, default=0,
+                   help="device-resident greedy evaluation of a bag network (dtqn_amd.agents.device_bag_eval.DeviceBagEvaluator): "
+                        "--device-eval-envs with one persistent-memory bag per evaluation environment kept, filled and chosen on the GPU.  "
+                        "Needs --bag-size K > 0; not with --eval-envs > 1 or --device-eval-envs; 0 = off")
     return p.parse_args(argv)
 
 
@@ -160,7 +165,8 @@ def train(agent, envs, eval_envs, env_strs, total_steps, eps, eval_frequency, ev
     iterations only account for them), which keeps one update per env step.  The vector steps are driven by the updates still
     owed, not by `timestep % N`: a resumed run steps on its first iteration, and the time limit is only honoured at a
     vector-step boundary, so a checkpoint's `num_train_steps` always equals the loop's timestep.
-    evaluators: one VectorEvaluator (--eval-envs N > 1) or DeviceEvaluator (--device-eval-envs N) per entry of env_strs, used instead
+    evaluators: one VectorEvaluator (--eval-envs N > 1), DeviceEvaluator (--device-eval-envs N) or DeviceBagEvaluator
+    (--device-bag-eval-envs N) per entry of env_strs, used instead
     of evaluate() on eval_envs."""
     start = time()
     agent.eval_off()
@@ -246,6 +252,16 @@ def run_experiment(args):
             raise ValueError("--device-eval-envs and --eval-envs > 1 exclude each other: the evaluation environments live on the device or on the host")
         if world > 1:
             raise NotImplementedError("--device-eval-envs: data-parallel runs are not covered")
+    if args.device_bag_eval_envs < 0:
+        raise ValueError("--device-bag-eval-envs must not be negative")
+    if args.device_bag_eval_envs > 0:
+        if args.eval_envs > 1 or args.device_eval_envs > 0:
+            raise ValueError("--device-bag-eval-envs excludes --eval-envs > 1 and --device-eval-envs: one evaluator per domain")
+        if args.bag_size < 1:
+            raise ValueError("--device-bag-eval-envs is the device-resident evaluation of a bag network: it needs --bag-size K > 0 "
+                             "(without a bag: --device-eval-envs)")
+        if world > 1:
+            raise NotImplementedError("--device-bag-eval-envs: data-parallel runs are not covered")
     cap = args.max_episode_steps if args.max_episode_steps > 0 else None     # tabular POMDPs: their step cap (a .pomdp path needs one)
     envs = [env_processing.make_env(e, cap) for e in args.envs]
     eval_envs = [env_processing.make_env(e, cap) for e in args.envs]
@@ -285,7 +301,7 @@ def run_experiment(args):
             raise NotImplementedError("--device-envs steps copies of ONE training domain")
         from dtqn_amd.agents.device_rollout import DeviceVectorActor
         actor_cls = DeviceVectorActor
-        if args.bag_size > 0:                      # the bags on the device as well; evaluation goes through evaluate() / --eval-envs
+        if args.bag_size > 0:                      # the bags on the device as well (their evaluation: --device-bag-eval-envs)
             from dtqn_amd.agents.device_bag import DeviceBagVectorActor
             actor_cls = DeviceBagVectorActor
         # the step cap is the registry entry's; an explicit --max-episode-steps (it sizes the replay's rows) caps the device
@@ -336,6 +352,11 @@ def run_experiment(args):
         evaluators = [DeviceEvaluator(agent, env_str, args.device_eval_envs, args.seed + 1000 * (rank + 1) + 700 + d,
                                       max_episode_steps=args.max_episode_steps if args.max_episode_steps > 0 else None,
                                       max_episodes=max(1, args.eval_episodes)) for d, env_str in enumerate(args.envs)]
+    if args.device_bag_eval_envs > 0:
+        from dtqn_amd.agents.device_bag_eval import DeviceBagEvaluator
+        evaluators = [DeviceBagEvaluator(agent, env_str, args.device_bag_eval_envs, args.seed + 1000 * (rank + 1) + 700 + d,
+                                         max_episode_steps=args.max_episode_steps if args.max_episode_steps > 0 else None,
+                                         max_episodes=max(1, args.eval_episodes)) for d, env_str in enumerate(args.envs)]
     train(agent, envs, eval_envs, args.envs, args.num_steps, eps, args.eval_frequency, args.eval_episodes, policy_path,
           args.save_policy, logger, mean_success_rate, mean_reward, mean_episode_length, time_remaining, args.verbose, is_main,
           overlap=args.overlap, vector=vector, evaluators=evaluators)
