@@ -6,7 +6,7 @@ import torch
 
 from oracle import dtqn_oracle as O
 
-from autograd_helpers import hip_grads
+from autograd_helpers import check_f64_under_masks, forward_masks, hip_grads
 from helpers import flat_from_params, padding_mask
 
 SEED, STEP = 12345, 7
@@ -27,18 +27,20 @@ CASES = {
 BATCH = 3
 
 
-def oracle_grads_drop(cfg: O.NetCfg, params, obs, act, bag, w, drop, probe=None):
-    """loss = (Q * w).sum() through oracle.forward under the keep masks of `drop`: q, {canonical key: grad}, d loss / d obss."""
+def oracle_grads_drop(cfg: O.NetCfg, params, obs, act, bag, w, drop, probe=None, dtype=torch.float32):
+    """loss = (Q * w).sum() through oracle.forward under the keep masks of `drop`: q, {canonical key: grad}, d loss / d obss.
+    dtype float64: the float32 parameters and inputs widened exactly, every operation in double."""
     keys = O.trainable_keys(cfg)
+    params = {k: v.to(dtype) if v.dtype == torch.float32 else v for k, v in params.items()}
     leaves = {k: params[k].detach().clone().requires_grad_(True) for k in keys}
     p2 = {k: leaves.get(O.canonical_key(cfg, k), params[k]) for k in O.state_dict_keys(cfg)}
-    o = torch.tensor(obs, dtype=torch.float32, requires_grad=True) if not cfg.discrete else torch.as_tensor(obs).long()
+    o = torch.tensor(obs, dtype=dtype, requires_grad=True) if not cfg.discrete else torch.as_tensor(obs).long()
     kw = {}
     if bag is not None:
-        kw = dict(bag_obss=torch.as_tensor(bag[0]).long() if cfg.discrete else torch.as_tensor(bag[0], dtype=torch.float32),
+        kw = dict(bag_obss=torch.as_tensor(bag[0]).long() if cfg.discrete else torch.as_tensor(bag[0], dtype=dtype),
                   bag_actions=torch.as_tensor(bag[1]))
     q = O.forward(p2, cfg, o, torch.as_tensor(act), probe, drop, **kw)
-    loss = (q * torch.as_tensor(w)).sum()
+    loss = (q * torch.as_tensor(w).to(dtype)).sum()
     wrt = [leaves[k] for k in keys] + ([o] if not cfg.discrete else [])
     g = torch.autograd.grad(loss, wrt)
     return q.detach().numpy(), dict(zip(keys, g)), (g[-1].numpy() if not cfg.discrete else None)
@@ -52,7 +54,7 @@ def flat_grad(m) -> np.ndarray:
     return flat.numpy()
 
 
-def hip_grads_drop(m, obs, act, bag, w, keys, device="cpu"):
+def hip_grads_drop(m, obs, act, bag, w, keys, device="cpu", masks_out=None):
     """autograd_helpers.hip_grads with the forward given the keep-mask keys (seed, step)."""
     o = torch.tensor(obs, device=device, requires_grad=not m.discrete)
     kw = dict(_train_dropout=keys)
@@ -61,6 +63,8 @@ def hip_grads_drop(m, obs, act, bag, w, keys, device="cpu"):
     m.zero_grad(set_to_none=True)
     q = m(o, torch.as_tensor(act, device=device), **kw)
     assert q.requires_grad and q.grad_fn is not None
+    if masks_out is not None:
+        masks_out.extend(forward_masks(q, m.net.num_layers, m.net.d_real or m.net.d_model))
     (q * torch.as_tensor(w, device=device)).sum().backward()
     return q.detach().cpu().numpy(), flat_grad(m), (None if o.grad is None else o.grad.cpu().numpy())
 
@@ -69,7 +73,8 @@ def check_dropout_parity(m, cfg, params, obs, act, bag, w, device="cpu", report=
     """Q, every parameter's gradient and obss.grad against the oracle under the masks of (SEED, STEP); the tolerances of
     autograd_helpers.check_against_oracle, every element compared (none is set aside for a ReLU kink).  The masks matter: without
     them the oracle's Q is somewhere else."""
-    q, got, dobs = hip_grads_drop(m, obs, act, bag, w, (SEED, STEP), device)
+    masks = []
+    q, got, dobs = hip_grads_drop(m, obs, act, bag, w, (SEED, STEP), device, masks_out=masks)
     drop = O.DropSpec(cfg.dropout, SEED, STEP, 0)
     q_ref, grads, dobs_ref = oracle_grads_drop(cfg, params, obs, act, bag, w, drop)
     q_plain = oracle_grads_drop(cfg, params, obs, act, bag, w, None)[0]
@@ -89,6 +94,8 @@ def check_dropout_parity(m, cfg, params, obs, act, bag, w, device="cpu", report=
         assert not got[pad].any()
     if dobs_ref is not None:
         assert dobs is not None and figures["dobs_err_over_max"] <= 2e-4, figures
+    check_f64_under_masks(cfg, m.net, got, masks, qmax,
+                          lambda probe, dtype: oracle_grads_drop(cfg, params, obs, act, bag, w, drop, probe, dtype)[1])
     return q, got, dobs
 
 

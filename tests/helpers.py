@@ -89,11 +89,12 @@ def flat_from_params(net, params, keys):
 
 
 def make_td_case(lib, cfg, *, seed, batch, T, n_eps, mask, history=None, tuf=10_000, lr=3e-4, device="cpu", test_lib=True,
-                 weight_scale=1.0):
+                 weight_scale=1.0, min_len=3):
     """Oracle learner + dtqn_amd TdEngine on identical parameters and an identical synthetic replay.
     weight_scale: factor on every weight MATRIX of the perturbed parameter set (0.1: std 0.2 -> 0.02, the init_weights scale of
     utils/torch_utils.py:4-15, with biases / LayerNorm / positions still moved off their init values: |Q| < 1, so the Q tolerance of
-    check_td_updates is the ABSOLUTE 1e-4 of north_star there)."""
+    check_td_updates is the ABSOLUTE 1e-4 of north_star there).
+    min_len: the shortest synthetic episode (1: windows that hold a single step of their episode can be drawn)."""
     import random as pyrandom
     from dtqn_amd.learner import DeviceReplay, TdEngine
     from oracle.replay_oracle import ReplayOracle, synth_fill
@@ -108,7 +109,8 @@ def make_td_case(lib, cfg, *, seed, batch, T, n_eps, mask, history=None, tuf=10_
     hist = cfg.history_len if history is None else history
     oracle = O.OracleLearner(cfg, pol, lr=lr, gamma=0.99, history=hist, tuf=tuf, target=tgt)
     host = ReplayOracle((n_eps + 2) * T, cfg.obs_dim, mask, T, cfg.history_len)
-    synth_fill(host, np.random.Generator(np.random.PCG64(seed + 1000)), n_eps, cfg.discrete, cfg.vocab_sizes, cfg.num_actions)
+    synth_fill(host, np.random.Generator(np.random.PCG64(seed + 1000)), n_eps, cfg.discrete, cfg.vocab_sizes, cfg.num_actions,
+               min_len=min_len)
     eng = TdEngine(net, batch, lr=lr, gamma=0.99, history=hist, tuf=tuf, _test_lib=lib if test_lib else None,
                    device=None if test_lib else device)
     eng.theta_pol.copy_(torch.from_numpy(pack_theta(net, pol)))
@@ -125,6 +127,13 @@ def engine_probe(cfg, net, eng):
     Bn, L, A = eng.batch, cfg.history_len, cfg.num_actions
     q3 = eng.q3.cpu().numpy().reshape(3, Bn, net.lp, net.ap)[:, :, :L, :A].copy()
     act = eng.act.cpu().numpy()[:Bn * net.act_stride].reshape(Bn, net.act_stride)
+    return {"masks": relu_masks(cfg, net, act, L), "argmax": torch.from_numpy(q3[1].argmax(-1))}
+
+
+def relu_masks(cfg, net, act, L):
+    """The ReLU activation patterns of rows [0, L) in the activation records act[B, net.act_stride] of a training forward (the TD
+    engine's, or the differentiable forward's workspace), in the order oracle.forward consumes them."""
+    Bn = act.shape[0]
     D = cfg.inner_embed_size
     fld = lambda off, w: torch.from_numpy(act[:, off:off + net.lp * w].reshape(Bn, net.lp, w)[:, :L].copy() > 0)
 
@@ -149,14 +158,14 @@ def engine_probe(cfg, net, eng):
     hh = fld(net.ao_hh, Dp)
     assert not hh[..., D:].any()
     masks.append(hh[..., :D])
-    return {"masks": masks, "argmax": torch.from_numpy(q3[1].argmax(-1))}
+    return masks
 
 
 ADAM_CHECK_TOTALS = [0.0, 0]         # seconds spent in / number of the per-step optimizer checks of check_td_updates, this process
 
 
 def check_td_updates(cfg, net, oracle, host, eng, rep, n_updates, q_tol=1e-4, grad_rtol=2e-4, one_call=False, q_rel=False,
-                     pipelined=False, draw_seed=1234, report_as=None):
+                     pipelined=False, draw_seed=1234, report_as=None, on_batch=None):
     """Run n_updates on both sides from identical (episode, start) draws and compare every stage:
     the three Q tensors, pre-clip gradients, statistics, parameters after the step.
     Every step is also an optimizer check on its own: the engine's post-step theta, exp_avg and exp_avg_sq against the float64
@@ -168,14 +177,20 @@ def check_td_updates(cfg, net, oracle, host, eng, rep, n_updates, q_tol=1e-4, gr
     kernels, policy passes as four row slices, the next update's target pass inside this update's backward launch -- or on the side
     stream for row-block nets): the engine draws its own windows, the oracle batch is built from the (episode, start) pairs the
     kernels left in ep_idx / start, everything else is compared as in the other modes.  The caller has enabled the pipeline.
+    Every gradient is also compared tensor by tensor and group by group with the oracle's float64 evaluation (grad_f64_helpers.py).
+    on_batch(it, eps, starts, batch): called with every update's drawn windows (cases that assert a property of their draw).
     report_as: name under which the worst absolute Q error / gradient error of the run go to gpurun_out/parity_report.json."""
     keys = O.trainable_keys(cfg)
     Bn, L, A = eng.batch, cfg.history_len, cfg.num_actions
     net = eng.net                  # the net the update runs on: the caller's, or its row-block twin (dtqn_td_prefers_tiled)
     worst = {"q_abs_err": 0.0, "q_abs_max": 0.0, "grad_err_over_max": 0.0, "updates": n_updates,
-             "adam_theta_over_bound": 0.0, "adam_m_over_bound": 0.0, "adam_v_over_bound": 0.0, "adam_check_seconds": 0.0}
+             "adam_theta_over_bound": 0.0, "adam_m_over_bound": 0.0, "adam_v_over_bound": 0.0, "adam_check_seconds": 0.0,
+             "grad64_over_bound": 0.0, "grad64_over_d32": 0.0, "grad64_rel_err": 0.0, "grad64_d32": 0.0, "grad64_group": None,
+             "grad64_checks": 0, "grad64_seconds": 0.0}
     import time
     from adam_f64_helpers import check_against_r32h, hyper_of
+    from grad_f64_helpers import check_gradient_f64, TOTALS as GRAD64_TOTALS
+    f64_every = True
     nt = net.n_trainable
     # the engine's pre-step optimizer state: taken here in the modes that step inside one call (the moments are then the zeros /
     # oracle values written below), in front of clip_adam otherwise
@@ -199,6 +214,8 @@ def check_td_updates(cfg, net, oracle, host, eng, rep, n_updates, q_tol=1e-4, gr
             eps, starts = host.sample_indices(Bn)
             batch = oracle_batch(host, eps, starts, cfg.discrete)
             eng.set_indices(eps, starts)
+        if on_batch is not None:
+            on_batch(it, eps, starts, batch)
         if cfg.bag_size > 0:       # a synthetic bag per window (the engine takes whatever the sampler hands it)
             rng = np.random.Generator(np.random.PCG64(77 + it))
             bo = rng.integers(0, cfg.vocab_sizes, (Bn, cfg.bag_size, cfg.obs_dim)).astype(np.float32) if cfg.discrete \
@@ -226,7 +243,10 @@ def check_td_updates(cfg, net, oracle, host, eng, rep, n_updates, q_tol=1e-4, gr
         D = cfg.inner_embed_size
         # dropout: the engine keys its keep masks by (dropout_seed, optimizer steps so far); the oracle evaluates the same hash
         drop = O.DropSpec(cfg.dropout, int(eng.td.dropout_seed), it) if cfg.dropout > 0 else None
+        probe64 = dict(probe, masks=list(probe["masks"]))      # the mask list is consumed: the float64 evaluation gets its own copy
+        t0 = time.perf_counter()
         grads, out = O.td_gradients(oracle.pol, oracle.tgt, cfg, batch, oracle.gamma, oracle.history, probe, drop)
+        t32 = time.perf_counter() - t0
         assert not probe["masks"], "oracle consumed fewer ReLU masks than the engine saved"
         n_relu = Bn * L * (6 * D * cfg.num_layers + D)
         assert probe.get("relu_flips", 0) <= max(2, n_relu // 20000), probe
@@ -251,6 +271,27 @@ def check_td_updates(cfg, net, oracle, host, eng, rep, n_updates, q_tol=1e-4, gr
         pad = padding_mask(net)
         if pad.any():                  # width-padded network: the padding takes no gradient at all
             assert not got[:net.n_trainable][pad].any(), (it, int(np.count_nonzero(got[:net.n_trainable][pad])))
+        # --- ... and tensor by tensor, group by group, against the oracle's float64 evaluation under the same masks and argmax choices,
+        # within what the fp32 oracle achieves on this batch (grad_f64_helpers.py).  Where float64 costs more than three times the fp32
+        # evaluation (measured at the first update), only the first and the last update of the case carry the check.
+        if f64_every or it in (0, n_updates - 1):
+            t0 = time.perf_counter()
+            g64, out64 = O.td_gradients64(oracle.pol, oracle.tgt, cfg, batch, oracle.gamma, oracle.history, probe64, drop)
+            t64 = time.perf_counter() - t0
+            assert not probe64["masks"] and out64[0].dtype == torch.float64
+            if it == 0:
+                f64_every = t64 <= 3.0 * t32
+            fig = check_gradient_f64(cfg, net, got, g64, grads, what=(it,))
+            for key, val in (("grad64_over_bound", fig["over_bound"]), ("grad64_over_d32", fig["over_d32"]), ("grad64_rel_err", fig["rel_err"]),
+                             ("grad64_d32", fig["d32"])):
+                if val >= worst[key]:
+                    worst[key] = val
+                    if key == "grad64_over_bound":
+                        worst["grad64_group"] = fig["group"]
+            worst["grad64_checks"] += 1
+            worst["grad64_seconds"] += time.perf_counter() - t0
+            GRAD64_TOTALS[0] += time.perf_counter() - t0
+            GRAD64_TOTALS[1] += 1
         # --- optimizer step + statistics
         if not one_call and not pipelined:
             snap = snapshot()

@@ -9,6 +9,7 @@ import torch
 from dtqn_amd import _binding as B
 from oracle import dtqn_oracle as O
 
+from grad_f64_cases import CASES as GROUP_CASES, draw_property
 from helpers import make_td_case, check_td_updates
 
 
@@ -37,6 +38,24 @@ def test_td_update_small_variants(emu, kw, run):
     net, oracle, host, eng, rep = make_td_case(emu, cfg, seed=21, batch=run["batch"], T=run["T"], n_eps=9, mask=run["mask"],
                                                history=run.get("history"), tuf=run.get("tuf", 10_000))
     check_td_updates(cfg, net, oracle, host, eng, rep, n_updates=3)
+
+
+@pytest.mark.parametrize("name", sorted(GROUP_CASES))
+def test_td_update_gradient_groups(emu, name):
+    """Cases in which a group of the float64 gradient check (grad_f64_helpers.py) is small, single or exactly zero: dead record rows and a
+    one-step window under the one-launch weight gradients at batch 32, a token seen once and one never, position rows reached through attention only (and
+    the same width-padded 48 -> 64), an action no loss row takes.  The property is asserted on the drawn windows (grad_f64_cases.py)."""
+    kw, run, lp = GROUP_CASES[name]
+    cfg = O.NetCfg(**kw)
+    net, oracle, host, eng, rep = make_td_case(emu, cfg, **run)
+    if name == "b32_dead_tokens":
+        assert net.lp == lp > cfg.history_len and emu.dtqn_td_wgrad_is_direct(ctypes.byref(net), run["batch"]) == 1     # one-launch weight gradients
+    if name == "short_history_d48":
+        assert net.d_real == 48 and net.d_model == 64
+    if name == "action_never_taken":
+        assert net.ap > cfg.num_actions
+    check_td_updates(cfg, net, oracle, host, eng, rep, n_updates=2, on_batch=draw_property(name, cfg, host, oracle.history),
+                     report_as=f"emu_groups_{name}")
 
 
 @pytest.mark.parametrize("kw,run", [CASES[1], CASES[2], CASES[6]])

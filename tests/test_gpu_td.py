@@ -10,6 +10,7 @@ from dtqn_amd import _binding as B
 from oracle import dtqn_oracle as O
 
 from conftest import GOLDEN
+from grad_f64_cases import CASES as GROUP_CASES, draw_property
 from helpers import make_td_case, check_td_updates, net_from_cfg, pack_theta, flat_from_params
 
 pytestmark = pytest.mark.gpu
@@ -107,6 +108,20 @@ def test_td_update_vs_oracle(lib, kw, run):
                                                device="cuda", test_lib=False)
     check_td_updates(cfg, net, oracle, host, eng, rep, n_updates=3, grad_rtol=run.get("grad_rtol", 2e-4))
     assert int(eng.xflags.sum()) == 0          # latency mode: every hand-over flag was lowered again
+
+
+@pytest.mark.parametrize("name", sorted(GROUP_CASES))
+def test_td_update_gradient_groups(lib, name):
+    """The cases of tests/grad_f64_cases.py on the device (the same windows as on the emulation: tests/test_emu_td.py): groups of the
+    float64 gradient check that are small, single or exactly zero, each property asserted on the drawn windows."""
+    import ctypes
+    kw, run, lp = GROUP_CASES[name]
+    cfg = O.NetCfg(**kw)
+    net, oracle, host, eng, rep = make_td_case(lib, cfg, device="cuda", test_lib=False, **run)
+    if name == "b32_dead_tokens":
+        assert net.lp == lp > cfg.history_len and lib.dtqn_td_wgrad_is_direct(ctypes.byref(net), run["batch"]) == 1     # one-launch weight gradients
+    check_td_updates(cfg, net, oracle, host, eng, rep, n_updates=2, on_batch=draw_property(name, cfg, host, oracle.history),
+                     report_as=f"gpu_groups_{name}")
 
 
 @pytest.mark.parametrize("kw,run", [CASES[2], CASES[6], CASES[9], CASES[13]])

@@ -110,11 +110,52 @@ def check_engine_vs_g11(lib, name, device="cpu", test_lib=True):
     worst = {k: float(np.abs(got[tab[k][0]:tab[k][0] + int(np.prod(tab[k][1]))] - ref_g[tab[k][0]:tab[k][0] + int(np.prod(tab[k][1]))]).max()) for k in keys}
     bad = {k: v / gmax for k, v in worst.items() if v > 2e-4 * gmax}
     assert not bad, (name, bad)
+    check_image_gradient_f64(name, z, cfg, pol, tgt, net, eng, got)
     eng.clip_adam()
     st = eng.read_stats()
     assert st["nonfinite"] == 0.0 and st["step"] == 1
     assert abs(st["td_error"] - float(z[f"{name}_loss"])) <= 2e-4 * max(1.0, float(z[f"{name}_loss"]))
     assert bool(torch.isfinite(eng.theta_pol).all())
+
+
+def image_conv_masks(cfg, eng):
+    """The ReLU patterns of the five convolutions in the encoder's activation workspace (dtqn_img_act_floats: one NHWC post-ReLU
+    feature map per layer over the B (L + 1) policy tokens, window-major), for rows 0 .. L-1 of every window -- the tokens of
+    policy(o) -- as [B L, C, H, W] booleans in the order oracle.embed_images consumes them."""
+    Bn, L = eng.batch, cfg.history_len
+    act = eng._img_act.cpu().numpy()
+    h, w = cfg.image[1], cfg.image[2]
+    masks, pos = [], 0
+    for _, co, s in O.IMG_CHANS:
+        h, w = (h - 1) // s + 1, (w - 1) // s + 1
+        n = Bn * (L + 1) * h * w * co
+        fmap = act[pos:pos + n].reshape(Bn, L + 1, h, w, co)[:, :L]
+        masks.append(torch.from_numpy(np.ascontiguousarray(fmap.reshape(Bn * L, h, w, co).transpose(0, 3, 1, 2)) > 0))
+        pos += n
+    return masks
+
+
+def check_image_gradient_f64(name, z, cfg, pol, tgt, net, eng, got):
+    """The engine's gradient against the oracle's float64 evaluation on the same pixel windows, group by group (grad_f64_helpers.py),
+    with the fp32 oracle as the yardstick: all three under the kernels' own ReLU patterns -- convolutions, transformer, head -- and
+    argmax choices, the number and size of the disagreements bounded as in helpers.check_td_updates."""
+    from grad_f64_helpers import check_gradient_f64
+    from helpers import engine_probe
+    L = cfg.history_len
+    batch = golden_batch(z, name, cfg)
+    probe = engine_probe(cfg, net, eng)
+    probe["conv_masks"] = image_conv_masks(cfg, eng)
+    n_relu = sum(int(m.numel()) for m in probe["masks"] + probe["conv_masks"])
+    p64 = dict(probe, masks=list(probe["masks"]), conv_masks=list(probe["conv_masks"]))
+    g32, out = O.td_gradients(pol, tgt, cfg, batch, 0.99, L, probe)
+    g64, _ = O.td_gradients64(pol, tgt, cfg, batch, 0.99, L, p64)
+    qmax = float(out[4].detach().abs().max())
+    for p in (probe, p64):
+        assert not p["masks"] and not p["conv_masks"], "oracle consumed fewer ReLU masks than the engine saved"
+        assert p.get("relu_flips", 0) <= max(2, n_relu // 20000), (name, {k: v for k, v in p.items() if "mask" not in k and k != "argmax"})
+        assert p.get("max_flip_preact", 0.0) <= 2e-5 * max(1.0, qmax), (name, p.get("max_flip_preact"))
+        assert p.get("argmax_flips", 0) <= 1
+    return check_gradient_f64(cfg, net, got, g64, g32, what=name)
 
 
 def check_module_forward_vs_g11(lib, device="cpu", tags=("a", "fwd144")):
