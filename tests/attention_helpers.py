@@ -9,6 +9,7 @@ import torch
 from oracle import dtqn_oracle as O
 
 from autograd_helpers import make_module
+from q_f64_helpers import check_q_f64, widen
 
 G13 = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "G13_attention.npz")
 
@@ -55,7 +56,34 @@ def captured(m):
     return alphas, bag
 
 
-def check_weights(alphas, bag, ref_alphas, ref_bag, atol=1e-5):
+def oracle_weights(cfg, params, inputs, wide=False):
+    """O.attention_weights on module inputs (g13_case / make_inputs: obss as float32, tokens included): ([alpha per layer], bag weights or
+    None) as numpy; wide: the float32 parameters, positions table and inputs widened exactly, every operation in float64."""
+    integer = cfg.discrete and cfg.image is None
+    as_obs = lambda a: torch.as_tensor(np.asarray(a)).long() if integer else torch.as_tensor(np.asarray(a, dtype=np.float32))
+    w = widen if wide else (lambda t: t)
+    kw = {}
+    if cfg.bag_size > 0:
+        kw = dict(bag_obss=w(as_obs(inputs["bag_obss"])), bag_actions=torch.as_tensor(np.asarray(inputs["bag_actions"])).long())
+    with torch.no_grad():
+        alphas, bag = O.attention_weights({k: w(v) for k, v in params.items()}, cfg, w(as_obs(inputs["obss"])),
+                                          torch.as_tensor(np.asarray(inputs["actions"])).long(), **kw)
+    return [a.numpy() for a in alphas], (None if bag is None else bag.numpy())
+
+
+def check_weights(alphas, bag, ref_alphas, ref_bag, atol=1e-5, f64=None):
+    """f64 = (cfg, params, inputs): the captured weights are also held, row by row at scale 1 (a row sums to 1), within margin * D32 of the
+    oracle's float64 softmax, D32 from its fp32 evaluation (q_f64_helpers.check_q_f64); the fp32 oracle weights themselves have to be the
+    reference weights handed in."""
+    if f64 is not None:
+        a32, b32 = oracle_weights(*f64)
+        a64, b64 = oracle_weights(*f64, wide=True)
+        for l, (a, r32, r64, ref) in enumerate(zip(alphas, a32, a64, ref_alphas)):
+            assert np.abs(r32 - ref).max() <= atol, ("oracle.attention_weights is not the reference's alpha", l, np.abs(r32 - ref).max())
+            check_q_f64(a, r64, r32, what=("alpha", l), scale=1.0)
+        if ref_bag is not None:
+            assert np.abs(b32 - ref_bag).max() <= atol, ("oracle.attention_weights is not the reference's bag weights", np.abs(b32 - ref_bag).max())
+            check_q_f64(bag, b64, b32, what="bag weights", scale=1.0)
     assert len(alphas) == len(ref_alphas)
     for l, (a, r) in enumerate(zip(alphas, ref_alphas)):
         assert a.shape == r.shape, (l, a.shape, r.shape)

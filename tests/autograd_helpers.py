@@ -8,6 +8,7 @@ from oracle import dtqn_oracle as O
 
 from grad_f64_helpers import check_gradient_f64
 from helpers import flat_from_params, pack_theta, padding_mask, relu_masks
+from q_f64_helpers import check_forward_f64
 
 
 def make_module(lib, cfg: O.NetCfg, params, device="cpu", autograd=True) -> DTQN:
@@ -95,6 +96,7 @@ def check_against_oracle(m: DTQN, cfg, params, obs, act, bag, w, device="cpu", r
     q_ref, grads, dobs_ref = oracle_grads(cfg, params, obs, act, bag, w)
     qmax = float(np.abs(q_ref).max())
     assert np.abs(q - q_ref).max() <= 1e-4 * max(1.0, qmax), (np.abs(q - q_ref).max(), qmax)
+    check_forward_f64(cfg, params, obs, act, q, bag=bag, what="differentiable forward")      # ... and row by row against float64
     ref = flat_from_params(m.net, grads, O.trainable_keys(cfg))
     err = np.abs(got - ref).max()
     assert err <= rtol * np.abs(ref).max(), (err, np.abs(ref).max())

@@ -177,7 +177,8 @@ def check_td_updates(cfg, net, oracle, host, eng, rep, n_updates, q_tol=1e-4, gr
     kernels, policy passes as four row slices, the next update's target pass inside this update's backward launch -- or on the side
     stream for row-block nets): the engine draws its own windows, the oracle batch is built from the (episode, start) pairs the
     kernels left in ep_idx / start, everything else is compared as in the other modes.  The caller has enabled the pipeline.
-    Every gradient is also compared tensor by tensor and group by group with the oracle's float64 evaluation (grad_f64_helpers.py).
+    Every gradient is also compared tensor by tensor and group by group with the oracle's float64 evaluation (grad_f64_helpers.py),
+    and the three Q tensors row by row with the float64 forwards of that same evaluation (q_f64_helpers.py).
     on_batch(it, eps, starts, batch): called with every update's drawn windows (cases that assert a property of their draw).
     report_as: name under which the worst absolute Q error / gradient error of the run go to gpurun_out/parity_report.json."""
     keys = O.trainable_keys(cfg)
@@ -186,10 +187,12 @@ def check_td_updates(cfg, net, oracle, host, eng, rep, n_updates, q_tol=1e-4, gr
     worst = {"q_abs_err": 0.0, "q_abs_max": 0.0, "grad_err_over_max": 0.0, "updates": n_updates,
              "adam_theta_over_bound": 0.0, "adam_m_over_bound": 0.0, "adam_v_over_bound": 0.0, "adam_check_seconds": 0.0,
              "grad64_over_bound": 0.0, "grad64_over_d32": 0.0, "grad64_rel_err": 0.0, "grad64_d32": 0.0, "grad64_group": None,
-             "grad64_checks": 0, "grad64_seconds": 0.0}
+             "grad64_checks": 0, "grad64_seconds": 0.0,
+             "q64_over_bound": 0.0, "q64_over_d32": 0.0, "q64_d32": 0.0, "q64_abs_bound": 0.0, "q64_row": None, "q64_checks": 0}
     import time
     from adam_f64_helpers import check_against_r32h, hyper_of
     from grad_f64_helpers import check_gradient_f64, TOTALS as GRAD64_TOTALS
+    from q_f64_helpers import check_q_f64, check_stats_f64
     f64_every = True
     nt = net.n_trainable
     # the engine's pre-step optimizer state: taken here in the modes that step inside one call (the moments are then the zeros /
@@ -274,6 +277,7 @@ def check_td_updates(cfg, net, oracle, host, eng, rep, n_updates, q_tol=1e-4, gr
         # --- ... and tensor by tensor, group by group, against the oracle's float64 evaluation under the same masks and argmax choices,
         # within what the fp32 oracle achieves on this batch (grad_f64_helpers.py).  Where float64 costs more than three times the fp32
         # evaluation (measured at the first update), only the first and the last update of the case carry the check.
+        q64_stats = None
         if f64_every or it in (0, n_updates - 1):
             t0 = time.perf_counter()
             g64, out64 = O.td_gradients64(oracle.pol, oracle.tgt, cfg, batch, oracle.gamma, oracle.history, probe64, drop)
@@ -288,6 +292,20 @@ def check_td_updates(cfg, net, oracle, host, eng, rep, n_updates, q_tol=1e-4, gr
                     worst[key] = val
                     if key == "grad64_over_bound":
                         worst["grad64_group"] = fig["group"]
+            # --- the three Q tensors row by row against the float64 forwards that evaluation already holds (q_f64_helpers.py): q_all under
+            # the engine's ReLU patterns on all three sides, the two next-state forwards under each evaluation's own
+            q64_stats = {"ref": out64[3], "q_h": out64[1].detach().numpy(), "t_h": out64[2].detach().numpy(),
+                         "qt": out64[6].detach().gather(2, out64[7]).squeeze(-1)[:, -oracle.history:].numpy()}
+            for w, name in enumerate(("q_all", "q_next_pol", "q_next_tgt")):
+                qf = check_q_f64(q3[w], out64[4 + w].detach().numpy(), out[4 + w].detach().numpy(), what=(it, name))
+                for key, val in (("q64_over_bound", qf["over_bound"]), ("q64_over_d32", qf["over_d32"]), ("q64_d32", qf["d32"]),
+                                 ("q64_abs_bound", qf["abs_bound"])):
+                    if val >= worst[key]:
+                        worst[key] = val
+                        if key == "q64_over_bound":
+                            worst["q64_row"] = [name] + qf["row"]
+                worst["q64_checks"] += 1
+                q64_stats[name] = qf["row_bound"][:, -oracle.history:]
             worst["grad64_checks"] += 1
             worst["grad64_seconds"] += time.perf_counter() - t0
             GRAD64_TOTALS[0] += time.perf_counter() - t0
@@ -316,6 +334,10 @@ def check_td_updates(cfg, net, oracle, host, eng, rep, n_updates, q_tol=1e-4, gr
         assert st["step"] == it + 1
         for k in ("td_error", "grad_norm", "qvalue_max", "qvalue_mean", "qvalue_min", "target_max", "target_mean", "target_min"):
             assert st[k] == ref_stats[k] or abs(st[k] - ref_stats[k]) <= 2e-4 * max(1.0, abs(ref_stats[k])), (it, k, st[k], ref_stats[k])
+        if q64_stats is not None:      # ... and against the float64 statistics, within the bounds the rows of Q hand down (q_f64_helpers.py)
+            over, _ = check_stats_f64(st, q64_stats["ref"], q64_stats["q_h"], q64_stats["t_h"], q64_stats["qt"], q64_stats["q_all"],
+                                      q64_stats["q_next_tgt"], oracle.gamma, Bn, oracle.history, what=(it, "statistics"))
+            worst["stat64_over_bound"] = max(worst.get("stat64_over_bound", 0.0), max(over.values()))
         post = eng.theta_pol.cpu().numpy()[:net.n_trainable].copy()
         assert not post[pad].any()     # ... and stays zero through the optimizer step
         ref_post = flat_from_params(net, oracle.pol, keys)

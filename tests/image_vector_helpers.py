@@ -6,6 +6,8 @@ import torch
 
 from oracle import dtqn_oracle as O
 
+from q_f64_helpers import check_forward_f64, check_pooled_f64
+
 L, D, H, NL, A = 6, 64, 8, 1, 4
 REUSE_ENV = "DTQN_IMG_ACTOR_REUSE"
 
@@ -102,6 +104,11 @@ def check_step(agent, vec, shape, q, where, oracle=True):
         err, bound = float(np.abs(q - ref).max()), 1e-4 * max(1.0, float(np.abs(ref).max()))
         print(where, "max |q - oracle| =", err, "bound", bound)
         assert err <= bound, (where, err, bound)
+        params = {k: v.detach().cpu().clone() for k, v in agent.policy_network.state_dict().items()}
+        pool = []                 # ... and the reported row of every environment against float64, one yardstick for the step
+        for i, p in enumerate(pre):
+            check_forward_f64(oracle_cfg(shape), params, p[None], None, q[i:i + 1], what=(where, "env", i), pool=pool)
+        check_pooled_f64(pool)
     return pre
 
 

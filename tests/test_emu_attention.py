@@ -32,7 +32,7 @@ def test_weights_match_the_reference(emu, z, name):
     q = m(**tensors(inputs)).numpy()
     assert np.abs(q - q_ref).max() <= 1e-4 * max(1.0, float(np.abs(q_ref).max()))
     alphas, bag = captured(m)
-    check_weights(alphas, bag, ref_alphas, ref_bag)
+    check_weights(alphas, bag, ref_alphas, ref_bag, f64=(cfg, params, inputs))
     assert m.bag_attn_weights is None                      # the reference declares it and never writes it (dtqn.py:135)
     # Q with capture on is the forward with capture off, bit for bit; a second capture gives the same bits
     m.set_capture_attention(False)
@@ -89,7 +89,7 @@ def test_autograd_with_capture(emu, z, name):
     q1, g1, d1 = hip_grads(m, obs, act, bag, w)
     assert np.array_equal(q0, q1) and np.array_equal(g0, g1) and np.array_equal(d0, d1)
     alphas, bagw = captured(m)
-    check_weights(alphas, bagw, ref_alphas, ref_bag)
+    check_weights(alphas, bagw, ref_alphas, ref_bag, f64=(cfg, params, inputs))
     with torch.no_grad():
         m(**tensors(inputs))
     nograd, bag2 = captured(m)

@@ -11,6 +11,7 @@ from dtqn_amd import _binding as B
 from oracle import dtqn_oracle as O
 
 from helpers import net_from_cfg, pack_theta, ptr
+from q_f64_helpers import check_forward_f64, check_pooled_f64
 
 
 @pytest.fixture(scope="module")
@@ -52,6 +53,7 @@ def test_forward_small_variants(emu, kw):
     cfg = O.NetCfg(**kw)
     params = O.init_params(cfg, seed=3, perturb=True)
     rng = np.random.default_rng(5)
+    pool = []                  # the float64 check: one yardstick over the rows of every context length
     for n in sorted({1, 2, cfg.history_len // 2, cfg.history_len}):
         Bn = 3
         if cfg.discrete:
@@ -65,6 +67,8 @@ def test_forward_small_variants(emu, kw):
         got = _fwd(emu, cfg, params, obs, act)
         assert np.isfinite(got).all()
         assert np.abs(got - ref).max() <= 1e-4, (n, np.abs(got - ref).max())
+        check_forward_f64(cfg, params, obs, act, got, what=("small variant", n), pool=pool)
+    check_pooled_f64(pool)
 
 
 def test_forward_cfg1_size(emu):
@@ -77,6 +81,7 @@ def test_forward_cfg1_size(emu):
         ref = O.forward(params, cfg, torch.as_tensor(obs), torch.as_tensor(act)).numpy()
     got = _fwd(emu, cfg, params, obs, act)
     assert np.abs(got - ref).max() <= 1e-4
+    check_forward_f64(cfg, params, obs, act, got, what="cfg-1 size")
 
 
 TILED = [
@@ -98,6 +103,7 @@ def test_tiled_forward_path(emu, kw, monkeypatch):
     params = O.init_params(cfg, seed=3, perturb=True)
     theta = pack_theta(net, params)
     rng = np.random.default_rng(5)
+    pool = []
     for n in sorted({1, cfg.history_len // 2 + 1, cfg.history_len}):
         Bn = 2
         obs = (rng.integers(0, cfg.vocab_sizes, size=(Bn, n, cfg.obs_dim)) if cfg.discrete
@@ -113,6 +119,8 @@ def test_tiled_forward_path(emu, kw, monkeypatch):
         rc = emu.dtqn_forward_tiled(ctypes.byref(net), ptr(theta), ptr(obs_f), ptr(act_u8), Bn, n, ptr(q), ptr(ws), None)
         assert rc == 0
         assert np.abs(q - ref).max() <= 1e-4, (n, np.abs(q - ref).max())
+        check_forward_f64(cfg, params, obs, act, q, what=("row-block path", n), pool=pool)
+    check_pooled_f64(pool)
     # the whole-sequence kernels refuse a tiled net, and the training entry points are not built for it
     assert emu.dtqn_forward(ctypes.byref(net), ptr(theta), ptr(obs_f), ptr(act_u8), Bn, n, ptr(q), None) == B.DEFINES["DTQN_ERR_CONFIG"]
 
@@ -138,6 +146,7 @@ def test_variants_beyond_the_lds_tile_take_the_tiled_path(emu):
     ws = np.zeros(emu.dtqn_forward_workspace_floats(ctypes.byref(net), 1), dtype=np.float32)
     assert emu.dtqn_forward_tiled(ctypes.byref(net), ptr(theta), ptr(obs), ptr(act), 1, 9, ptr(q), ptr(ws), None) == 0
     assert np.abs(q - ref).max() <= 1e-4
+    check_forward_f64(cfg, params, obs, act, q, what="D 128 GRU routed to the row-block path")
 
 
 @pytest.mark.parametrize("kw", [dict(obs_dim=3, num_actions=3, inner_embed_size=64, num_heads=8, num_layers=2, history_len=50),
@@ -155,6 +164,7 @@ def test_actor_forward_one_call(emu, kw, monkeypatch):
     assert need > 0 and net.tiled == 0
     ws = np.zeros(need, dtype=np.float32)
     rng = np.random.default_rng(11)
+    pool = []
     for n in (1, 20, 33, L):
         obs = rng.uniform(-1, 1, size=(1, n, Odim)).astype(np.float32)
         act = rng.integers(0, A, size=(1, n, 1))
@@ -171,8 +181,10 @@ def test_actor_forward_one_call(emu, kw, monkeypatch):
                                         None if workspace is None else ptr(workspace), 0, 0, 0, None)
             assert rc == 0
             assert np.abs(q_last - ref).max() <= 1e-4, (n, workspace is None)
+            check_forward_f64(cfg, params, obs, act, q_d[None, :n], what=("actor", n, workspace is None), pool=pool)      # every row the actor leaves
             assert np.array_equal(q_last, q_d[n - 1])
         assert not ws[emu.dtqn_td_xch_floats(ctypes.byref(net), 1):].any()      # hand-over flags lowered again
+    check_pooled_f64(pool)             # one sequence per call: the yardstick is taken over the rows of all of them
     assert emu.dtqn_actor_forward(ctypes.byref(net), ptr(theta), ptr(ctx_h), ptr(ctx_d), L + 1, ptr(q_d), ptr(q_last), None, 0, 0, 0, None) == B.DEFINES["DTQN_ERR_ARG"]
 
 
@@ -196,6 +208,7 @@ def test_forward_with_a_bag(emu, kw):
     assert params["ffn.0.weight"].shape == (cfg.inner_embed_size, 2 * cfg.inner_embed_size)
     theta = pack_theta(net, params)
     rng = np.random.default_rng(6)
+    pool = []
     for n in sorted({1, cfg.history_len // 2 + 1, cfg.history_len}):
         Bn = 3
         draw = lambda m: (rng.integers(0, cfg.vocab_sizes, size=(Bn, m, cfg.obs_dim)) if cfg.discrete
@@ -215,6 +228,8 @@ def test_forward_with_a_bag(emu, kw):
                                   ptr(q), ptr(ws), 0, 0, 0, None)
         assert rc == 0
         assert np.abs(q - ref).max() <= 1e-4, (n, np.abs(q - ref).max())
+        check_forward_f64(cfg, params, obs, act, q, bag=(bag_obs, bag_act), what=("bag", n), pool=pool)
+    check_pooled_f64(pool)
     # the bag-less entry refuses a bag network
     assert emu.dtqn_forward_tiled(ctypes.byref(net), ptr(theta), ptr(f32(obs)), ptr(u8(act)), Bn, n, ptr(q), ptr(ws), None) != 0
 

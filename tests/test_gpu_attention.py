@@ -35,7 +35,7 @@ def test_weights_match_the_reference_on_device(lib, z, name):
     q = m(**tensors(inputs, "cuda"))
     assert np.abs(q.cpu().numpy() - q_ref).max() <= 1e-4 * max(1.0, float(np.abs(q_ref).max()))
     alphas, bag = captured(m)
-    check_weights(alphas, bag, ref_alphas, ref_bag)
+    check_weights(alphas, bag, ref_alphas, ref_bag, f64=(cfg, params, inputs))
     assert all(layer.alpha.device.type == "cuda" for layer in m.transformer_layers)
     m.set_capture_attention(False)
     assert torch.equal(q, m(**tensors(inputs, "cuda")))
@@ -106,7 +106,8 @@ def test_weights_match_multihead_attention(lib, name, kw, Bn, n):
     kwb = {} if bag is None else dict(bag_obss=torch.as_tensor(bag[0], device="cuda"), bag_actions=torch.as_tensor(bag[1], device="cuda"))
     q = m(torch.as_tensor(obs, device="cuda"), torch.as_tensor(act, device="cuda"), **kwb)
     alphas, bagw = captured(m)
-    check_weights(alphas, bagw, ref_alphas, ref_bag)
+    check_weights(alphas, bagw, ref_alphas, ref_bag,
+                  f64=(cfg, params, dict(obss=obs, actions=act, **({} if bag is None else dict(bag_obss=bag[0], bag_actions=bag[1])))))
     m.set_capture_attention(False)
     assert torch.equal(q, m(torch.as_tensor(obs, device="cuda"), torch.as_tensor(act, device="cuda"), **kwb))
 

@@ -8,6 +8,7 @@ import torch
 from oracle import dtqn_oracle as O
 
 from helpers import check_td_updates, make_td_case
+from q_f64_helpers import check_forward_f64
 
 pytestmark = pytest.mark.gpu
 
@@ -65,6 +66,7 @@ def test_forward_at_512_vs_oracle(lib):
         got = hip_forward(lib, cfg, params, obs, act)
         assert np.isfinite(got).all()
         assert np.abs(got - ref).max() <= 1e-4 * max(1.0, np.abs(ref).max()), (n, np.abs(got - ref).max())
+        check_forward_f64(cfg, params, obs, act, got, what=("forward at 512", n))
 
 
 def _update_once(lib, cfg, batch, seed=5):
@@ -115,6 +117,7 @@ def test_image_network_forward_at_150(lib):
         ref = O.forward(pol, cfg, obs).numpy()
     assert np.isfinite(q).all()
     assert np.abs(q - ref).max() <= 1e-4 * max(1.0, np.abs(ref).max()), np.abs(q - ref).max()
+    check_forward_f64(cfg, pol, obs.numpy(), None, q, what="image network at 150")
 
 
 def test_agent_trains_at_a_512_step_context():

@@ -7,6 +7,7 @@ import torch
 
 from oracle import dtqn_oracle as O
 
+from q_f64_helpers import check_forward_f64
 from bag_mfma_helpers import LDS_BYTES, OVERFLOW, agent_train_run, bag_weights, launched, one_update, resident_bwd_lds, small_cfg
 
 pytestmark = pytest.mark.gpu
@@ -63,6 +64,7 @@ def test_forward_bag_on_a_partial_context(lib):
     qmax = float(np.abs(q_ref).max())
     print("forward_bag partial context: err", float(np.abs(q - q_ref).max()), "|Q|max", qmax)
     assert np.abs(q - q_ref).max() <= 1e-4 * max(1.0, qmax)
+    check_forward_f64(cfg, params, obs, act, q, bag=bag, what="forward_bag on a partial context")
 
 
 def test_agent_train_beyond_the_resident_tile_is_finite_and_deterministic(lib, monkeypatch, capfd):

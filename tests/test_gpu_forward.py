@@ -12,6 +12,7 @@ from oracle import dtqn_oracle as O
 
 from conftest import GOLDEN
 from helpers import net_from_cfg, pack_theta, ptr
+from q_f64_helpers import check_forward_f64, check_pooled_f64
 
 pytestmark = pytest.mark.gpu
 
@@ -50,10 +51,13 @@ def test_golden_G4_actor_variable_length(lib):
     for tag in ("res", "gru_a8_sin"):          # residual gate; GRU gate + action embedding + sinusoidal encodings
         cfg = O.NetCfg(**json.loads(str(z[f"{tag}/cfg"])))
         params = O.init_params(cfg, seed=41, perturb=True)
+        pool = []              # the float64 check: one yardstick over the rows of every prefix length
         for n in (1, 2, 17, 50):
             got = hip_forward(lib, cfg, params, z[f"{tag}/n{n}_obs"], z[f"{tag}/n{n}_act"])
             ref = z[f"{tag}/n{n}_q"]
             assert np.abs(got - ref).max() <= Q_TOL * max(1.0, np.abs(ref).max()), (tag, n)
+            check_forward_f64(cfg, params, z[f"{tag}/n{n}_obs"], z[f"{tag}/n{n}_act"], got, what=("G4", tag, n), pool=pool)
+        check_pooled_f64(pool)
 
 
 def test_golden_G1_q_values(lib):
@@ -65,10 +69,13 @@ def test_golden_G1_q_values(lib):
     scale = 1.0          # absolute tolerance
     got = hip_forward(lib, cfg, pol, z["batch0_obss"], z["batch0_actions"])
     assert np.abs(got - z["q_all"]).max() <= Q_TOL * scale
+    check_forward_f64(cfg, pol, z["batch0_obss"], z["batch0_actions"], got, what=("G1", "q_all"))
     got = hip_forward(lib, cfg, pol, z["batch0_next_obss"], z["batch0_next_actions"])
     assert np.abs(got - z["q_next_pol"]).max() <= Q_TOL * scale
+    check_forward_f64(cfg, pol, z["batch0_next_obss"], z["batch0_next_actions"], got, what=("G1", "q_next_pol"))
     got = hip_forward(lib, cfg, tgt, z["batch0_next_obss"], z["batch0_next_actions"])
     assert np.abs(got - z["q_next_tgt"]).max() <= Q_TOL * scale
+    check_forward_f64(cfg, tgt, z["batch0_next_obss"], z["batch0_next_actions"], got, what=("G1", "q_next_tgt"))
 
 
 def test_golden_G3_cfg345_q_values(lib):
@@ -88,6 +95,7 @@ def test_golden_G3_cfg345_q_values(lib):
             got = hip_forward(lib, cfg, params, z[p + obs_k], z[p + act_k])
             err = np.abs(got - z[p + q_k]).max()
             assert err <= Q_TOL * scale, (name, q_k, err, scale)
+            check_forward_f64(cfg, params, z[p + obs_k], z[p + act_k], got, what=("G3", name, q_k))
 
 
 VARIANTS = [
@@ -122,6 +130,7 @@ def test_variants_vs_oracle(lib, kw):
     cfg = O.NetCfg(**kw)
     params = O.init_params(cfg, seed=3, perturb=True)
     rng = np.random.default_rng(5)
+    pool = []
     for n in sorted({1, 2, cfg.history_len // 2, cfg.history_len}):
         Bn = 5
         obs = (rng.integers(0, cfg.vocab_sizes, size=(Bn, n, cfg.obs_dim)) if cfg.discrete
@@ -133,6 +142,8 @@ def test_variants_vs_oracle(lib, kw):
         got = hip_forward(lib, cfg, params, obs, act)
         assert np.isfinite(got).all()
         assert np.abs(got - ref).max() <= Q_TOL * max(1.0, np.abs(ref).max()), (n, np.abs(got - ref).max())     # std-0.2 stress weights
+        check_forward_f64(cfg, params, obs, act, got, what=("variant", n), pool=pool)
+    check_pooled_f64(pool)
 
 
 def test_seq_longer_than_context_is_rejected(lib):

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 import torch
 
+from q_f64_helpers import check_forward_f64
 from test_image_golden import NAMES, check_engine_vs_g11, check_module_forward_vs_g11
 
 pytestmark = pytest.mark.gpu
@@ -124,6 +125,7 @@ def test_full_size_minihack_crop_update_properties(lib):
     with torch.no_grad():
         ref = O.forward(pol, cfg, torch.as_tensor(rows[0, 0:L].reshape(1, L, 3, 144, 144))).numpy()[0]
     assert np.abs(q4[0, 0] - ref).max() <= 1e-4 * max(1.0, np.abs(ref).max())
+    check_forward_f64(cfg, pol, rows[0, 0:L].reshape(1, L, 3, 144, 144), None, q4[0, 0:1], what="MiniHack crop, window 0")
 
 
 def test_image_replay_producer_is_bit_exact(lib):

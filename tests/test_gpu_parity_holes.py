@@ -23,6 +23,7 @@ from oracle import replay_oracle as RO
 
 from conftest import GOLDEN, REPO
 from helpers import make_td_case, check_td_updates, net_from_cfg, pack_theta, ptr
+from q_f64_helpers import check_forward_f64, check_pooled_f64
 
 pytestmark = pytest.mark.gpu
 
@@ -197,6 +198,7 @@ def test_golden_G4_through_actor_forward(lib):
         theta_d = torch.from_numpy(pack_theta(net, params)).cuda()
         split_capable = lib.dtqn_td_row_split(ctypes.byref(net), 1) >= 2
         assert split_capable                                   # D = 64, 64-row tile: both gates are covered
+        pool = []
         for n in (1, 2, 17, 50):
             obs, act, ref = z[f"{tag}/n{n}_obs"][0], z[f"{tag}/n{n}_act"][0].reshape(-1), z[f"{tag}/n{n}_q"][0]
             for use_ws in (True, False):
@@ -206,6 +208,7 @@ def test_golden_G4_through_actor_forward(lib):
                 assert err <= 1e-4, (tag, n, use_ws, err)
                 assert np.array_equal(q_last, q_all[n - 1])
                 assert np.abs(q_all[:n] - ref).max() <= 1e-4
+                check_forward_f64(cfg, params, obs[None], act[None], q_all[None, :n], what=("G4 actor", tag, n, use_ws), pool=pool)
         rng = np.random.default_rng(17)
         for n in (31, 32, 33, 34, 36, 49):
             obs = rng.uniform(-1, 1, size=(n, cfg.obs_dim)).astype(np.float32)
@@ -218,6 +221,8 @@ def test_golden_G4_through_actor_forward(lib):
                 worst = max(worst, err / max(1.0, np.abs(ref).max()))
                 assert err <= 1e-4, (tag, n, use_ws, err)
                 assert np.array_equal(q_last, q_all[n - 1])
+                check_forward_f64(cfg, params, obs[None], act[None], q_all[None, :n], what=("actor", tag, n, use_ws), pool=pool)
+        check_pooled_f64(pool)         # one sequence per call: one yardstick over the rows of all the calls of this net
     report("actor_forward_max_rel_err", worst)
 
 
@@ -229,6 +234,7 @@ def test_actor_forward_on_the_tiled_path(lib):
     assert net.tiled == 1
     theta_d = torch.from_numpy(pack_theta(net, params)).cuda()
     rng = np.random.default_rng(2)
+    pool = []
     for n in (1, 63, 65, 128):
         obs = rng.integers(0, 11, size=(n, 6)).astype(np.float32)
         act = rng.integers(0, 6, size=n)
@@ -237,6 +243,8 @@ def test_actor_forward_on_the_tiled_path(lib):
         q_last, q_all = _actor_forward(lib, net, theta_d, obs, act, True)
         assert np.abs(q_all[:n] - ref).max() <= 1e-4, n
         assert np.array_equal(q_last, q_all[n - 1])
+        check_forward_f64(cfg, params, obs[None].astype(np.int64), act[None], q_all[None, :n], what=("actor on the row-block path", n), pool=pool)
+    check_pooled_f64(pool)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -290,7 +298,7 @@ def test_q_values_absolute_tolerance_at_init_scale(lib, name):
     kw, Bn = BASELINE_SHAPES[name]
     cfg = O.NetCfg(**kw)
     rng = np.random.default_rng(31)
-    worst = 0.0
+    worst, bound = 0.0, 0.0
     for variant in ("init", "moved"):
         params = O.init_params(cfg, seed=13, perturb=(variant == "moved"))
         if variant == "moved":
@@ -308,4 +316,6 @@ def test_q_values_absolute_tolerance_at_init_scale(lib, name):
         err = float(np.abs(got - ref).max())
         worst = max(worst, err)
         assert np.abs(ref).max() < 1.0 and err <= 1e-4, (name, variant, err, np.abs(ref).max())
+        bound = max(bound, check_forward_f64(cfg, params, obs, act, got, what=("init scale", name, variant))["abs_bound"])
     report(f"q_abs_err_init_scale_{name}", worst)
+    report(f"q64_abs_bound_init_scale_{name}", bound)

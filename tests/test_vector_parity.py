@@ -12,6 +12,7 @@ from dtqn_amd import _binding as B
 from oracle import dtqn_oracle as O
 
 from helpers import net_from_cfg, pack_theta, ptr
+from q_f64_helpers import check_forward_f64, check_pooled_f64
 
 
 def run_batch(lib, net, theta, obs_list, act_list, device, stream=None, lens_override=None, n_max_override=None):
@@ -88,6 +89,7 @@ def check_batched_actor_vs_oracle(lib, kw, sizes, device="cpu", stream=None, rou
             act = [rng.integers(0, cfg.num_actions, size=n) for n in lens]
             rc, q_last, q_all = run_batch(lib, net, theta, obs, act, device, stream)
             assert rc == 0, (N, rnd, rc)
+            pool = []         # the float64 check of the round: one yardstick over the rows of every environment
             for i, n in enumerate(lens):
                 with torch.no_grad():
                     ref = O.forward(params, cfg, torch.as_tensor(obs[i][None], dtype=ot), torch.as_tensor(act[i][None, :, None], dtype=torch.long)).numpy()[0]
@@ -97,6 +99,8 @@ def check_batched_actor_vs_oracle(lib, kw, sizes, device="cpu", stream=None, rou
                 assert err <= 1e-4 * scale, (N, rnd, i, n, err)                          # north_star: Q within 1e-4
                 assert np.abs(q_all[i, :n] - ref).max() <= 1e-4 * scale, (N, rnd, i, n)  # every live row, not only the reported one
                 assert np.array_equal(q_last[i], q_all[i, n - 1])
+                check_forward_f64(cfg, params, obs[i][None], act[i][None], q_all[i:i + 1, :n], what=("batched actor", N, rnd, i, n), pool=pool)
+            check_pooled_f64(pool)
     return worst
 
 
