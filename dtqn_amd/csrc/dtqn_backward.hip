@@ -947,6 +947,7 @@ extern "C" int dtqn_td_backward_ahead(const DtqnNet* net, const DtqnReplay* rp, 
 static int td_backward(const DtqnNet* net, const DtqnReplay* rp, const DtqnTd* td, const DtqnTd* td_next, int draw_step_next, void* stream) {
     if (!net || !rp || !td || td->batch < 1) return DTQN_ERR_ARG;
     if (td->history < 1 || td->history > net->ctx_len) return DTQN_ERR_ARG;
+    if (net->dropout > 0.f && td->batch > DTQN_MAX_DROP_BATCH) return DTQN_ERR_ARG;     // the mask key's sequence field (dtqn_device.hpp Drop.salt)
     if (net->tiled) return td_next ? DTQN_ERR_CONFIG : tiled_td_backward(net, rp, td, (hipStream_t)stream);
     if (bwd_lds_bytes(net) > 160 * 1024) return DTQN_ERR_CONFIG;
     BwdArgs a;

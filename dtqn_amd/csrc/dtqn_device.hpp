@@ -702,8 +702,13 @@ __device__ __forceinline__ bool drop_keep(const Drop& d, int site, int layer, ui
 __device__ __forceinline__ float drop_apply(const Drop& d, int site, int layer, uint32_t idx, float v) {
     return d.thresh == 0u ? v : (drop_keep(d, site, layer, idx) ? v * d.scale : 0.f);
 }
-// element index of an attention probability: (head, query row, key row), rows of up to 256
-__device__ __forceinline__ uint32_t drop_attn_idx(int h, int trow, int s) { return ((uint32_t)h << 16) | ((uint32_t)trow << 8) | (uint32_t)s; }
+// element index of an attention probability or a bag weight: (head < 64, query row < 512, key row or bag entry < 512), one value
+// each.  Bits 0-7 and 8-15 hold the low eight bits of key and query row, bits 16-21 the head; the ninth bits of query row and key sit
+// above the head field, at 22 and 23, so every index with both rows below 256 is head << 16 | query << 8 | key.
+__device__ __forceinline__ uint32_t drop_attn_idx(int h, int trow, int s) {
+    const uint32_t t = (uint32_t)trow, k = (uint32_t)s;
+    return ((uint32_t)h << 16) | ((t & 255u) << 8) | (k & 255u) | ((t >> 8) << 22) | ((k >> 8) << 23);
+}
 
 // Causal attention work is triangular: the 64-item block of query rows [8g, 8g+8) costs ~8(g+1) key steps
 // (the reverse for the key-row pass of the backward).  Waves w and w + NW/2 share a SIMD (waves are dealt to

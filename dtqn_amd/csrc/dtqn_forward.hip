@@ -24,6 +24,7 @@ static int dispatch_fwd(const FwdArgs& a, int nseq, int row_split, hipStream_t s
     const int D = a.net.d_model, HD = a.net.head_dim;
     const int MT = mt_rows > 0 ? mt_rows : a.net.lp / 16;
     const int NW = mt_rows > 0 ? 8 : waves_for(a.net);
+    if (a.drop_thresh != 0u && a.batch > DTQN_MAX_DROP_BATCH) return DTQN_ERR_ARG;      // the mask key's sequence field (dtqn_device.hpp Drop.salt)
     if (dtqn_ws_lite(a.net.tiled, D, HD, a.net.d_real)) {      // four slices or one workgroup per sequence, nothing else (dtqn_limits.h)
         if (a.net.identity || a.net.gate != DTQN_GATE_RES || mt_rows > 0 || (row_split == 4 && (!a.xch || !a.xflags))) return DTQN_ERR_CONFIG;
         const bool pad = a.net.d_real > 0;
@@ -158,6 +159,7 @@ static int td_forward_part(const DtqnNet* net, const DtqnReplay* rp, const DtqnT
     if (!net || !rp || !td || td->batch < 1) return DTQN_ERR_ARG;
     if (rp->obs_dim != net->obs_dim || rp->max_steps < net->ctx_len) return DTQN_ERR_ARG;
     if (pass0 < 0 || npasses < 1 || pass0 + npasses > 3) return DTQN_ERR_ARG;
+    if (net->dropout > 0.f && td->batch > DTQN_MAX_DROP_BATCH) return DTQN_ERR_ARG;      // the mask key's sequence field (dtqn_device.hpp Drop.salt)
     const bool whole = pass0 == 0 && npasses == 3;
     const bool draw = td->sample_in_kernel != 0;
     if (draw) {

@@ -6,7 +6,8 @@
 #define DTQN_MAX_D 128          /* d_model instantiations: 64, 128 (and 16/32 for tests) */
 #define DTQN_MAX_HEAD_DIM 128   /* 4 .. 128 in the row-block attention kernels (whole-head tile while it fits LDS, key-blocked beyond: dtqn_attn_whole_tile); the whole-sequence kernels: 8, 16 (and 32: dtqn_ws_lite) */
 #define DTQN_MAX_ACTIONS 64
-#define DTQN_MAX_BAG 256        /* bag entries (bag_size <= padded context <= 256, the row-block tiled path's limit) */
+#define DTQN_MAX_BAG 256        /* bag entries dtqn_replay_gather_bag draws from an episode; the attention kernels take a caller's bag of up to the padded context (dtqn_net_init) */
+#define DTQN_MAX_DROP_BATCH 1048576   /* sequences per pass of a launch that draws dropout masks: the mask key holds the sequence in 20 bits (dtqn_device.hpp Drop.salt) */
 #define DTQN_THREADS 256        /* 4 wave64 per workgroup */
 #define DTQN_WAVES 4
 

@@ -126,6 +126,8 @@ static inline TlDrop tl_drop_make(const DtqnNet& net, uint32_t seed, uint32_t st
     }
     return d;
 }
+// the sequence of a mask key has 20 bits below the pass (Drop.salt): a launch that draws masks takes no more sequences per pass
+static inline bool tl_drop_ok(const TlDrop& d) { return d.thresh == 0u || d.batch <= DTQN_MAX_DROP_BATCH; }
 __device__ __forceinline__ Drop tl_drop(const TlDrop& d, int s) {
     if (d.thresh == 0u) return drop_off();
     const int which = s / d.batch;
@@ -4525,6 +4527,7 @@ int tiled_td_forward_part(const DtqnNet* net, const DtqnReplay* rp, const DtqnTd
     const int split = 2 * td->batch - src.seq0 > 0 ? 2 * td->batch - src.seq0 : 0;     // sequences of passes 0 - 1 use theta_pol
     // policy(o) and policy(o') run in train mode, the target net in eval mode (dtqn.py:215-230); step = optimizer steps so far
     const TlDrop drop = tl_drop_make(*net, td->dropout_seed, 0u, td->step_counter, td->batch, 0x3);
+    if (!tl_drop_ok(drop)) return DTQN_ERR_ARG;
     // the first forward launch of an update rewrites the fragment-major weight copies from the parameters as they are NOW
     if (pass0 == 0) {
         const int rc = dtqn_td_wpack(net, td, stream);
@@ -4554,6 +4557,7 @@ int tiled_td_backward(const DtqnNet* net, const DtqnReplay* rp, const DtqnTd* td
     in.n = net->ctx_len;
     // the training forward's dropout (pass 0 of the TD update), recomputed: step = step_counter[1], not yet advanced
     in.drop = tl_drop_make(*net, td->dropout_seed, 0u, td->step_counter, td->batch, 0x1);
+    if (!tl_drop_ok(in.drop)) return DTQN_ERR_ARG;
     switch (net->d_model) {
         case 64: return backward_records<64>(*net, in, *td, stream);
         case 128: return backward_records<128>(*net, in, *td, stream);
@@ -4599,6 +4603,7 @@ static int forward_tiled_impl(const DtqnNet* net, const float* theta, const floa
     const long long qs = (long long)n * net->num_actions;
     // a train-mode forward of the actor (the reference's policy network stays in train mode during rollouts): one pass, sequence = salt
     const TlDrop drop = tl_drop_make(*net, drop_seed, drop_step, nullptr, batch, train_mode ? 0x1 : 0);
+    if (!tl_drop_ok(drop)) return DTQN_ERR_ARG;
     switch (net->d_model) {
         case 64: return forward_records<64>(*net, theta, theta, batch, src, batch, n, workspace, false, q_out, qs, net->num_actions, s, drop);
         case 128: return forward_records<128>(*net, theta, theta, batch, src, batch, n, workspace, false, q_out, qs, net->num_actions, s, drop);
@@ -4770,6 +4775,7 @@ extern "C" int dtqn_forward_train_drop(const DtqnNet* net, const float* theta, c
     hipStream_t s = (hipStream_t)stream;
     // without dropout: the function the no-grad forward computes (its default), with the records of a training forward
     const TlDrop drop = tl_drop_make(*net, dropout_seed, (uint32_t)dropout_step, nullptr, batch, dropout_step >= 0 ? 0x1 : 0);
+    if (!tl_drop_ok(drop)) return DTQN_ERR_ARG;
     switch (net->d_model) {
         case 64: return forward_records<64>(*net, theta, theta, batch, src, batch, n, workspace, true, q_out, qs, net->num_actions, s, drop);
         case 128: return forward_records<128>(*net, theta, theta, batch, src, batch, n, workspace, true, q_out, qs, net->num_actions, s, drop);
@@ -4788,6 +4794,8 @@ extern "C" int dtqn_backward_dq_drop(const DtqnNet* net, const float* theta, con
     if (net->action_dim > 0 && !actions) return DTQN_ERR_ARG;
     if (net->bag_size > 0 && (!bag_obs || (net->action_dim > 0 && !bag_actions))) return DTQN_ERR_ARG;
     if (dobs != nullptr && net->discrete) return DTQN_ERR_ARG;     // tokens have no gradient
+    const TlDrop drop = tl_drop_make(*net, dropout_seed, (uint32_t)dropout_step, nullptr, batch, dropout_step >= 0 ? 0x1 : 0);
+    if (!tl_drop_ok(drop)) return DTQN_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     const GradWs w = grad_ws(*net, batch);
     DtqnTd td = {};
@@ -4809,7 +4817,7 @@ extern "C" int dtqn_backward_dq_drop(const DtqnNet* net, const float* theta, con
     in.src.ep_idx = nullptr; in.src.start = nullptr; in.src.batch = batch;
     in.src.bag_obs = bag_obs; in.src.bag_actions = bag_actions; in.src.bag_batch = batch;
     in.n = n;
-    in.drop = tl_drop_make(*net, dropout_seed, (uint32_t)dropout_step, nullptr, batch, dropout_step >= 0 ? 0x1 : 0);
+    in.drop = drop;
     int rc;
     switch (net->d_model) {
         case 64: rc = backward_records<64>(*net, in, td, s); break;

@@ -694,8 +694,7 @@ class RefDropoutHash:
         assert m == cfg.bag_size and BH % H == 0, input.shape
         self.log.append(("bag", self.which, tuple(input.shape)))
         Bn = BH // H
-        idx = ((np.arange(H)[:, None, None] << 16) | (np.arange(n)[None, :, None] << 8) | np.arange(m)[None, None, :]).astype(np.uint64)
-        keep = np.stack([O.drop_keep(spec, b, O.DROP_BAG, 0, idx) for b in range(Bn)])
+        keep = np.stack([O.bag_keep(spec, b, np.arange(H), np.arange(n), np.arange(m)) for b in range(Bn)])
         return input * torch.from_numpy(keep.astype(np.float32) * np.float32(spec.scale)).reshape(BH, n, m)
 
 
