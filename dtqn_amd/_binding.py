@@ -76,6 +76,7 @@ DtqnTd = _make("DtqnTd")
 DtqnRollout = _make("DtqnRollout")
 DtqnDevBag = _make("DtqnDevBag")
 DtqnEval = _make("DtqnEval")
+DrqnNet = _make("DrqnNet")
 
 
 def load_library(path: str) -> ctypes.CDLL:
@@ -170,6 +171,11 @@ def load_library(path: str) -> ctypes.CDLL:
         "dtqn_forward_train_drop": [P(DtqnNet), vp, vp, vp, vp, vp, i32, i32, vp, vp, u32, i32, vp],
         "dtqn_backward_dq_drop": [P(DtqnNet), vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, u32, i32, vp],
         "dtqn_attn_weights": [P(DtqnNet), vp, i32, i32, vp, vp, vp],
+        "dtqn_drqn_net_init": [P(DrqnNet)],
+        "dtqn_drqn_workspace_floats": [P(DrqnNet), i32, i32, i32],
+        "dtqn_drqn_forward": [P(DrqnNet), vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp],
+        "dtqn_drqn_forward_train": [P(DrqnNet), vp, vp, vp, i32, i32, vp, vp, vp, vp, vp],
+        "dtqn_drqn_backward": [P(DrqnNet), vp, vp, i32, i32, vp, vp, vp, vp],
         "dtqn_xch_publish": [vp, i32, vp],
         "dtqn_td_xreduce": [P(DtqnNet), P(DtqnTd), vp, vp, i32, i32, vp, vp, vp, vp],
         "dtqn_td_update": [P(DtqnNet), P(DtqnReplay), P(DtqnTd), vp],
@@ -188,7 +194,8 @@ def load_library(path: str) -> ctypes.CDLL:
             ctypes.c_longlong if name in ("dtqn_img_act_floats", "dtqn_img_gact_floats", "dtqn_img_wpart_floats",
                                                     "dtqn_grad_workspace_floats", "dtqn_img_actor_stage_bytes",
                                                     "dtqn_img_actor_workspace_floats", "dtqn_rollout_state_bytes", "dtqn_pomdp_table_bytes",
-                                                    "dtqn_deval_state_bytes", "dtqn_devbag_state_bytes") else ctypes.c_int)
+                                                    "dtqn_deval_state_bytes", "dtqn_devbag_state_bytes",
+                                                    "dtqn_drqn_workspace_floats") else ctypes.c_int)
     assert set(protos) == set(FUNCTIONS), sorted(set(protos) ^ set(FUNCTIONS))
     if lib.dtqn_abi_version() != DEFINES["DTQN_ABI_VERSION"]:
         raise OSError(f"{path}: ABI version {lib.dtqn_abi_version()} != header {DEFINES['DTQN_ABI_VERSION']}")
@@ -330,3 +337,45 @@ def pad_param(net: DtqnNet, key: str, real, padded_shape):
     rg, pg = _grids(net, key, real.shape, padded_shape)
     out.reshape(pg)[tuple(slice(0, r) for r in rg)] = real.reshape(rg)        # reshape of the fresh contiguous `out` is a view
     return out
+
+
+# ---- DRQN baseline (include/dtqn_hip.h, DrqnNet) -----------------------------------------------------------------------------
+def make_drqn_net(lib, *, obs_dim, num_actions, embed_per_obs_dim=8, action_dim=0, inner_embed=64, context_len=50, discrete=False,
+                  vocab_sizes=0) -> DrqnNet:
+    """Build and initialise a DrqnNet from the reference's DRQN constructor arguments (dtqn/networks/drqn.py:12-32)."""
+    if isinstance(obs_dim, (tuple, list)):
+        raise NotImplementedError("DRQN: image observations are outside the gfx950 LSTM kernels' coverage; see DESIGN.md")
+    net = DrqnNet()
+    net.obs_dim, net.num_actions, net.embed_per_obs, net.action_dim = int(obs_dim), int(num_actions), int(embed_per_obs_dim), int(action_dim)
+    net.d_model, net.ctx_len = int(inner_embed), int(context_len)
+    net.discrete, net.vocab = int(bool(discrete)), int(vocab_sizes or 0)
+    rc = lib.dtqn_drqn_net_init(ctypes.byref(net))
+    if rc != 0:
+        tok, cols, tab = DISCRETE_LIMITS
+        raise NotImplementedError(
+            f"dtqn_drqn_net_init rc={rc}: this DRQN shape is outside the gfx950 kernels' coverage (D={inner_embed} in 64 / 128 / 256, "
+            f"L={context_len} <= 512; discrete observations: obs_dim <= {tok}, obs_dim * embed_per_obs <= {cols}, "
+            f"vocab * embed_per_obs <= {tab}); see DESIGN.md")
+    return net
+
+
+def drqn_param_table(net: DrqnNet) -> Dict[str, Tuple[int, Tuple[int, ...]]]:
+    """state_dict key -> (offset into theta, shape), in the reference's registration order (dqn.py:24-51, drqn.py:33-35)."""
+    D, A = net.d_model, net.num_actions
+    tab: Dict[str, Tuple[int, Tuple[int, ...]]] = {}
+    if net.discrete:
+        tab["obs_embed.observation_embedding.0.weight"] = (net.off_obs_tab, (net.vocab, net.embed_per_obs))
+        tab["obs_embed.observation_embedding.2.weight"] = (net.off_obs_w, (D, net.ke))
+        tab["obs_embed.observation_embedding.2.bias"] = (net.off_obs_b, (D,))
+    else:
+        tab["obs_embed.observation_embedding.weight"] = (net.off_obs_w, (D, net.ke))
+        tab["obs_embed.observation_embedding.bias"] = (net.off_obs_b, (D,))
+    tab["ffn.0.weight"] = (net.off_head1_w, (D, D))
+    tab["ffn.0.bias"] = (net.off_head1_b, (D,))
+    tab["ffn.2.weight"] = (net.off_head2_w, (A, D))
+    tab["ffn.2.bias"] = (net.off_head2_b, (A,))
+    tab["lstm.weight_ih_l0"] = (net.off_w_ih, (4 * D, D))
+    tab["lstm.weight_hh_l0"] = (net.off_w_hh, (4 * D, D))
+    tab["lstm.bias_ih_l0"] = (net.off_b_ih, (4 * D,))
+    tab["lstm.bias_hh_l0"] = (net.off_b_hh, (4 * D,))
+    return tab

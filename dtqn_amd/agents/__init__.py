@@ -2,10 +2,13 @@
 spells it `DTQNAgent` -- both resolve to the same class.  Resolved on first access so that importing the package does not
 load the gfx950 engine."""
 
-__all__ = ["DtqnAgent", "DTQNAgent", "VectorActor"]
+__all__ = ["DtqnAgent", "DTQNAgent", "DrqnAgent", "VectorActor"]
 
 
 def __getattr__(name):
+    if name == "DrqnAgent":
+        from .drqn import DrqnAgent
+        return DrqnAgent
     if name in ("DtqnAgent", "DTQNAgent"):
         from .dtqn import DtqnAgent
         return DtqnAgent

@@ -4,14 +4,17 @@ from typing import Sequence
 import numpy as np
 import torch
 
+from ..agents.drqn import DrqnAgent
 from ..agents.dtqn import DtqnAgent
+from ..networks.drqn import DRQN
 from ..networks.dtqn import DTQN
 from . import env_processing
 
-# The reference also registers LSTM / MLP baselines (ADRQN, DRQN, DARQN, DQN) here; they are a
-# different model family and outside this engine's scope.
-MODEL_MAP = {"DTQN": DTQN}
-AGENT_MAP = {"DTQN": DtqnAgent}
+# The reference also registers ADRQN, DARQN and DQN here.  Its DQN never advances its context or passes an episode length to the
+# replay, and its DARQN constructor does not match the factory call; ADRQN is DRQN with an action embedding.  DRQN, the recurrent
+# baseline the method is measured against, runs on the engine's LSTM kernels; the other three are not implemented.
+MODEL_MAP = {"DTQN": DTQN, "DRQN": DRQN}
+AGENT_MAP = {"DTQN": DtqnAgent, "DRQN": DrqnAgent}
 
 
 def get_agent(model_str: str, envs: Sequence, embed_per_obs_dim: int, action_dim: int, inner_embed: int,
@@ -23,7 +26,7 @@ def get_agent(model_str: str, envs: Sequence, embed_per_obs_dim: int, action_dim
     share observation and action spaces.  Positional order = the reference's, so run.py-style
     call sites work unchanged."""
     if model_str not in MODEL_MAP:
-        raise NotImplementedError(f"model {model_str!r}: dtqn_amd implements {sorted(MODEL_MAP)} (DTQN hot path only)")
+        raise NotImplementedError(f"model {model_str!r}: dtqn_amd implements {sorted(MODEL_MAP)}")
     env0 = envs[0]
     obs_len = env_processing.get_env_obs_length(env0)
     obs_mask = env_processing.get_env_obs_mask(env0)
@@ -39,7 +42,14 @@ def get_agent(model_str: str, envs: Sequence, embed_per_obs_dim: int, action_dim
     num_actions = env0.action_space.n
     device = torch.device(device)
 
+    def make_model():
+        """The non-transformer models (the reference's make_model, utils/agent_utils.py:112-123); `context_len` bounds one forward."""
+        return MODEL_MAP[model_str](obs_len, num_actions, embed_per_obs_dim, action_dim, inner_embed, discrete, obs_vocab_size=vocab,
+                                    batch_size=batch_size, context_len=context_len).to(device)
+
     def network_factory():
+        if "DTQN" not in model_str:
+            return make_model()
         return MODEL_MAP[model_str](
             obs_len, num_actions, embed_per_obs_dim, action_dim, inner_embed, num_heads, num_layers, context_len,
             dropout=dropout, gate=gate, identity=identity, pos=pos, discrete=discrete, vocab_sizes=vocab,

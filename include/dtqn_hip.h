@@ -845,6 +845,83 @@ int dtqn_backward_dq_drop(const DtqnNet* net, const float* theta, const float* o
  * Recomputed from the q | k | v records and the row log-sum-exp (no second softmax pass); deterministic, no atomics */
 int dtqn_attn_weights(const DtqnNet* net, const float* workspace, int batch, int n, float* alpha_out, float* bag_out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * DRQN baseline (dtqn/networks/drqn.py): observation embedding -> one-layer LSTM (torch.nn.LSTM: gate order i, f, g, o, both
+ * biases) -> Linear, ReLU, Linear on every row.  A network of its own beside DtqnNet: its own struct, its own flat theta, its own
+ * entry points (dtqn_drqn_*, dtqn_drqn.hip).  The recurrent scans give 16 sequences to one workgroup for all time steps; no workgroup
+ * waits for another.  The fused TD update, the device-resident rollouts and data parallelism do not cover it: DrqnAgent's update is
+ * written in torch on dtqn_amd.networks.DRQN.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct DrqnNet {
+    /* set by the caller */
+    int32_t obs_dim;          /* O */
+    int32_t num_actions;      /* A */
+    int32_t embed_per_obs;    /* e (discrete observations) */
+    int32_t action_dim;       /* accepted and unused, as in the reference's DRQN */
+    int32_t d_model;          /* D: embedding width = LSTM hidden size (64, 128, 256) */
+    int32_t ctx_len;          /* L <= 512 */
+    int32_t discrete;
+    int32_t vocab;            /* V (discrete observations) */
+    /* filled by dtqn_drqn_net_init */
+    int32_t ke;               /* input columns of the observation Linear: O, or O * e for discrete observations */
+    int32_t kep;              /* ke padded to 4 */
+    int32_t ap;               /* A padded to 4 */
+    /* flat theta (floats); every tensor contiguous at the reference's shape */
+    int32_t off_obs_tab;      /* [V][e]    obs_embed.observation_embedding.0.weight (discrete; -1 otherwise) */
+    int32_t off_obs_w;        /* [D][ke]   obs_embed.observation_embedding(.2).weight */
+    int32_t off_obs_b;        /* [D] */
+    int32_t off_w_ih;         /* [4D][D]   lstm.weight_ih_l0 */
+    int32_t off_w_hh;         /* [4D][D]   lstm.weight_hh_l0 */
+    int32_t off_b_ih;         /* [4D] */
+    int32_t off_b_hh;         /* [4D] */
+    int32_t off_head1_w;      /* [D][D]    ffn.0 */
+    int32_t off_head1_b;      /* [D] */
+    int32_t off_head2_w;      /* [A][D]    ffn.2 */
+    int32_t off_head2_b;      /* [A] */
+    int32_t n_trainable;      /* every float of theta is trainable */
+    int32_t n_theta;          /* n_trainable padded to 4 */
+    /* record of one row (token) in the workspace: rec_row floats at (b * n + t) * rec_row behind the workspace header */
+    int32_t rec_x;            /* [D]   embedding */
+    int32_t rec_gates;        /* [4D]  input projection + both biases; after a training forward the activated gates i | f | g | o */
+    int32_t rec_c;            /* [D]   cell state after the row (training forwards) */
+    int32_t rec_h;            /* [D]   LSTM output of the row: 0 at and beyond lengths[b] */
+    int32_t rec_z1;           /* [D]   ReLU(ffn.0) */
+    int32_t rec_e;            /* [kep] gathered table rows (discrete observations; -1 otherwise) */
+    int32_t rec_row;
+    /* gradient record of one row, behind the records of all rows (training workspaces) */
+    int32_t grec_dh;          /* [D]   dL/d(LSTM output) */
+    int32_t grec_dg;          /* [4D]  dL/d(gate pre-activations): 0 at and beyond lengths[b] */
+    int32_t grec_dz1;         /* [D] */
+    int32_t grec_dx;          /* [D]   dL/d(embedding) */
+    int32_t grec_de;          /* [kep] dL/d(gathered table rows) */
+    int32_t grec_row;
+} DrqnNet;
+
+/* Fills the derived fields.  DTQN_ERR_CONFIG: d_model other than 64 / 128 / 256, ctx_len outside 1..512, num_actions outside
+ * 1..DTQN_MAX_ACTIONS, a discrete observation outside the bounds of dtqn_limits.h, obs_dim < 1 (images have no DrqnNet) */
+int dtqn_drqn_net_init(DrqnNet* net);
+/* floats of the workspace of one call on `batch` sequences of n rows: header (the lengths) + records (+ gradient records when
+ * training != 0); 0 = not covered.  Never has to be zeroed */
+long long dtqn_drqn_workspace_floats(const DrqnNet* net, int batch, int n, int training);
+/* DRQN.forward (drqn.py:38-66).  obs [B][n][O] f32 on the device (discrete tokens as floats); lengths: int32[B] on the HOST or NULL;
+ * h0, c0 [B][D] on the device or NULL (zeros); q_out [B][n][A]; h_n, c_n [B][D] or NULL.
+ *   lengths given (packed-sequence mode): rows at or beyond lengths[b] have LSTM output exactly 0 -- their Q is the head of a zero
+ *   vector -- and the state stops at the last live row; any lengths[b] < 1 or > n: DTQN_ERR_ARG.  lengths NULL: every row is live.
+ *   h0 / c0 given (step mode): the state is carried in and out; n may be 1.
+ * The call copies the lengths to the device and waits for that copy, so the caller's array may go once it returns. */
+int dtqn_drqn_forward(const DrqnNet* net, const float* theta, const float* obs, const int32_t* lengths, const float* h0, const float* c0,
+                      int batch, int n, float* q_out, float* h_n, float* c_n, float* workspace, void* stream);
+/* The same forward from the zero state (same Q, h_n, c_n, bit for bit) that also keeps the records dtqn_drqn_backward reads:
+ * activated gates, cell and hidden rows.  workspace: dtqn_drqn_workspace_floats(net, batch, n, 1) floats */
+int dtqn_drqn_forward_train(const DrqnNet* net, const float* theta, const float* obs, const int32_t* lengths, int batch, int n,
+                            float* q_out, float* h_n, float* c_n, float* workspace, void* stream);
+/* dq [B][n][A] = dL/dQ of the last dtqn_drqn_forward_train on `workspace` (same theta, obs, batch, n)  ->  grad_out [n_trainable],
+ * WRITTEN, not accumulated: head backward, the reverse scan of backpropagation through time (no gradient enters through h_n / c_n),
+ * input projection, embedding (the table by a per-element sum in token order).  No float atomics; every sum runs in a fixed order:
+ * two calls give the same bits.  Records of rows at or beyond lengths[b] are never read (their ffn.0 output is ReLU of its bias). */
+int dtqn_drqn_backward(const DrqnNet* net, const float* theta, const float* obs, int batch, int n, const float* dq, float* workspace,
+                       float* grad_out, void* stream);
+
 /* Debug aid: when a device buffer of >= 2*64 int64 is registered, workgroup 0 of the forward (slots
  * 0..63) and backward (slots 64..127) TD kernels records the 100 MHz wall clock at its stage
  * boundaries into it.  NULL disables (default). */

@@ -7,7 +7,8 @@ running the DTQN hot path on the MI355X engine (dtqn_amd).
 Differences from the reference, all at the edges of the hot path:
   * `--envs` defaults to the LIST ["DiscreteCarFlag-v0"] (the reference's string default iterates
     over characters, SURVEY.md section 4 quirk 7);
-  * `--model` accepts DTQN only; `--render` is out of scope; pixel observations (`Box(0, 255, (C, H, W), uint8)`) run, with
+  * `--model` accepts DTQN and DRQN (the recurrent baseline: host environments, one at a time; the transformer-only flags are
+    ignored, as in the reference); `--render` is out of scope; pixel observations (`Box(0, 255, (C, H, W), uint8)`) run, with
     `--num-envs N` and `--eval-envs N` too;
   * new flags: `--sampler {reference,device}` (replay index draw on the host with Python's `random`
     stream like the reference, or on the GPU), `--ref-quirks` (reproduce the reference's
@@ -245,6 +246,15 @@ def run_experiment(args):
     rank, world, local = ddp.init_from_env("cuda" if args.device.startswith("cuda") else "cpu")
     is_main = rank == 0
     device = torch.device(args.device if world == 1 or not args.device.startswith("cuda") else f"cuda:{local}")
+    if args.model == "DRQN":
+        # the recurrent baseline steps one host environment and updates in torch on the LSTM kernels: nothing else covers it yet
+        excluded = [("--num-envs", args.num_envs > 1), ("--eval-envs", args.eval_envs > 1), ("--device-envs", args.device_envs != 0),
+                    ("--device-eval-envs", args.device_eval_envs != 0), ("--device-bag-eval-envs", args.device_bag_eval_envs != 0),
+                    ("--overlap", args.overlap), ("--bag-size", args.bag_size > 0), ("--sampler device", args.sampler == "device"),
+                    ("a world size above 1", world > 1)]
+        for switch, on in excluded:
+            if on:
+                raise NotImplementedError(f"--model DRQN: {switch} is not covered (host environments, one at a time, reference sampler)")
     if args.device_eval_envs < 0:
         raise ValueError("--device-eval-envs must not be negative")
     if args.device_eval_envs > 0:
