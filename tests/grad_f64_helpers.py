@@ -40,6 +40,13 @@ def groups_of(cfg: O.NetCfg, key: str, shape):
     return [(key, (), False)]                   # everything else, the shared GRU gate tensors (sum over layers) included: one tensor
 
 
+def scaled(err_max, ref_max, tmax, phi=PHI):
+    """(error / s, s) with s = max(group max, phi * tensor max) of the float64 value: the one scale rule of every float64 check
+    (scalars or arrays of groups; image_encoder_helpers.py applies it to feature maps and per-tap gradient tiles)."""
+    s = np.maximum(ref_max, phi * tmax)
+    return err_max / s, s
+
+
 def group_errors(cfg: O.NetCfg, got, g64, phi=PHI):
     """got, g64: {trainable key: reference-shaped array}.  -> ({group: max |got - g64| / s}, {group: s}, [structural-zero groups
     in which `got` has a non-zero entry]) with s = max(group max, phi * tensor max) of g64.  A selected row (groups_of) whose float64
@@ -60,8 +67,8 @@ def group_errors(cfg: O.NetCfg, got, g64, phi=PHI):
                 if np.any(h != 0.0):
                     nonzero.append((name, int(np.count_nonzero(h)), float(np.abs(h).max())))
                 continue
-            s = max(gmax, phi * tmax)
-            errs[name], scales[name] = float(np.abs(h - r).max() / s), s
+            e, s = scaled(float(np.abs(h - r).max()), gmax, tmax, phi)
+            errs[name], scales[name] = float(e), float(s)
     return errs, scales, nonzero
 
 
@@ -90,4 +97,4 @@ def check_gradient_f64(cfg: O.NetCfg, net, got_flat, g64, g32, margin=MARGIN, ph
     return fig
 
 
-__all__ = ["PHI", "MARGIN", "groups_of", "group_errors", "check_gradient_f64", "TOTALS"]
+__all__ = ["PHI", "MARGIN", "U32", "scaled", "groups_of", "group_errors", "check_gradient_f64", "TOTALS"]

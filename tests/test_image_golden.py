@@ -155,7 +155,14 @@ def check_image_gradient_f64(name, z, cfg, pol, tgt, net, eng, got):
         assert p.get("relu_flips", 0) <= max(2, n_relu // 20000), (name, {k: v for k, v in p.items() if "mask" not in k and k != "argmax"})
         assert p.get("max_flip_preact", 0.0) <= 2e-5 * max(1.0, qmax), (name, p.get("max_flip_preact"))
         assert p.get("argmax_flips", 0) <= 1
-    return check_gradient_f64(cfg, net, got, g64, g32, what=name)
+    fig = check_gradient_f64(cfg, net, got, g64, g32, what=name)
+    # and the encoder's tensors tap by tap and tile by tile (image_encoder_helpers.param_groups), where the tensor-wide groups above
+    # hold a wrong tap or a wrong 64-channel tile only to the tensor's maximum
+    from helpers import unpack_flat
+    from image_encoder_helpers import ENC_KEYS, check_param_groups
+    fig["encoder_tiles"] = check_param_groups(unpack_flat(net, np.asarray(got), ENC_KEYS), {k: g64[k].detach().numpy() for k in ENC_KEYS},
+                                              {k: g32[k].detach().numpy() for k in ENC_KEYS}, f"G11 {name} encoder tiles")
+    return fig
 
 
 def check_module_forward_vs_g11(lib, device="cpu", tags=("a", "fwd144")):
