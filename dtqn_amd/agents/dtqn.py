@@ -69,6 +69,11 @@ class _AdamHandle:
         e.pipeline_reset()
 
 
+def dropout_seed_of(sample_seed: int) -> int:
+    """The keep-mask seed of an agent whose window draws use `sample_seed`: a stream of its own."""
+    return int(sample_seed) + 0x5EED
+
+
 class DtqnAgent:
     # updates whose statistics may sit in the pinned ring before the host folds them into the running averages (a non-finite
     # gradient norm is therefore raised at most this many updates late; readers of the averages drain everything first)
@@ -98,7 +103,7 @@ class DtqnAgent:
         if sampler not in ("reference", "device"):
             raise ValueError("sampler must be 'reference' (Python `random` stream) or 'device'")
         self.engine = TdEngine(self.policy_network.net, batch_size, lr=learning_rate, gamma=gamma, history=history,
-                               tuf=target_update_frequency, grad_norm_clip=grad_norm_clip, dropout_seed=int(sample_seed) + 0x5EED,
+                               tuf=target_update_frequency, grad_norm_clip=grad_norm_clip, dropout_seed=dropout_seed_of(sample_seed),
                                device=None if self._test_mode else self.device,
                                _test_lib=lib if self._test_mode else None,
                                theta_pol=self.policy_network.flat, theta_tgt=self.target_network.flat)

@@ -238,6 +238,23 @@ def train(agent, envs, eval_envs, env_strs, total_steps, eps, eval_frequency, ev
                 return
 
 
+def sampler_seed(seed: int, rank: int) -> int:
+    """Seed of a rank's window and bag draws (--sampler device) and of its host streams."""
+    return seed + rank
+
+
+def rollout_seed(seed: int, rank: int) -> int:
+    """Seed of a rank's device-resident training environments; the base of its host-side environment copies."""
+    return seed + 1000 * (rank + 1)
+
+
+def evaluator_seed(seed: int, rank: int, domain: int) -> int:
+    """Seed of a rank's device-resident evaluator of evaluation domain `domain`.  The device draws of a run -- window (seed, step,
+    element, k), rollout (seed, vstep, env, k), evaluation -- go through one hash with overlapping draw indices: only distinct seeds
+    keep an environment's exploration bits from being a batch element's episode bits (tests/test_sampler_seeds.py)."""
+    return rollout_seed(seed, rank) + 700 + domain
+
+
 def run_experiment(args):
     start = time()
     if os.environ.get("DTQN_DEBUG_HANG_DUMP"):       # debugging aid: dump every thread's Python stack after N seconds (a rank stuck in a collective)
@@ -275,12 +292,12 @@ def run_experiment(args):
     cap = args.max_episode_steps if args.max_episode_steps > 0 else None     # tabular POMDPs: their step cap (a .pomdp path needs one)
     envs = [env_processing.make_env(e, cap) for e in args.envs]
     eval_envs = [env_processing.make_env(e, cap) for e in args.envs]
-    set_global_seed(args.seed + rank, *(envs + eval_envs))         # per-rank env / replay / exploration streams
+    set_global_seed(sampler_seed(args.seed, rank), *(envs + eval_envs))         # per-rank env / replay / exploration streams
     eps = epsilon_anneal.LinearAnneal(1.0, 0.1, args.num_steps // 10)
     agent = get_agent(args.model, envs, args.obs_embed, args.a_embed, args.in_embed, args.buf_size, device, args.lr,
                       args.batch, args.context, args.max_episode_steps, args.history, args.tuf, args.discount,
                       args.heads, args.layers, args.dropout, args.identity, args.gate, args.pos, args.bag_size,
-                      sampler=args.sampler, ref_quirks=args.ref_quirks, sample_seed=args.seed + rank)
+                      sampler=args.sampler, ref_quirks=args.ref_quirks, sample_seed=sampler_seed(args.seed, rank))
     if is_main:
         print(f"[ {timestamp()} ] Creating {args.model} with "
               f"{sum(p.numel() for p in agent.policy_network.parameters())} parameters", flush=True)
@@ -316,7 +333,7 @@ def run_experiment(args):
             actor_cls = DeviceBagVectorActor
         # the step cap is the registry entry's; an explicit --max-episode-steps (it sizes the replay's rows) caps the device
         # environments as well, so that an episode always fits its slot
-        vector = actor_cls(agent, args.envs[0], args.device_envs, args.seed + 1000 * (rank + 1),
+        vector = actor_cls(agent, args.envs[0], args.device_envs, rollout_seed(args.seed, rank),
                            max_episode_steps=args.max_episode_steps if args.max_episode_steps > 0 else None)
     if os.path.exists(policy_path + "_mini_checkpoint.pt"):
         done_steps = agent.load_mini_checkpoint(policy_path)["step"]
@@ -344,7 +361,7 @@ def run_experiment(args):
         # N copies of the (first) training domain, each with its own seed
         venvs = [env_processing.make_env(args.envs[k % len(args.envs)], cap) for k in range(args.num_envs)]
         for k, e in enumerate(venvs):
-            e.seed(args.seed + 1000 * (rank + 1) + k)
+            e.seed(rollout_seed(args.seed, rank) + k)
         vector = VectorActor(agent, venvs, ref_quirks=args.ref_quirks)
     evaluators = None
     if args.eval_envs > 1:
@@ -354,17 +371,17 @@ def run_experiment(args):
         for d, env_str in enumerate(args.envs):
             copies = [env_processing.make_env(env_str, cap) for _ in range(args.eval_envs)]
             for k, e in enumerate(copies):
-                e.seed(args.seed + 1000 * (rank + 1) + 500 + d * args.eval_envs + k)
+                e.seed(rollout_seed(args.seed, rank) + 500 + d * args.eval_envs + k)
             evaluators.append(VectorEvaluator(agent, copies, ref_quirks=args.ref_quirks))
     if args.device_eval_envs > 0:
         from dtqn_amd.agents.device_eval import DeviceEvaluator
         # one evaluator per evaluation domain, seeded in a range of its own; the step cap as for --device-envs
-        evaluators = [DeviceEvaluator(agent, env_str, args.device_eval_envs, args.seed + 1000 * (rank + 1) + 700 + d,
+        evaluators = [DeviceEvaluator(agent, env_str, args.device_eval_envs, evaluator_seed(args.seed, rank, d),
                                       max_episode_steps=args.max_episode_steps if args.max_episode_steps > 0 else None,
                                       max_episodes=max(1, args.eval_episodes)) for d, env_str in enumerate(args.envs)]
     if args.device_bag_eval_envs > 0:
         from dtqn_amd.agents.device_bag_eval import DeviceBagEvaluator
-        evaluators = [DeviceBagEvaluator(agent, env_str, args.device_bag_eval_envs, args.seed + 1000 * (rank + 1) + 700 + d,
+        evaluators = [DeviceBagEvaluator(agent, env_str, args.device_bag_eval_envs, evaluator_seed(args.seed, rank, d),
                                          max_episode_steps=args.max_episode_steps if args.max_episode_steps > 0 else None,
                                          max_episodes=max(1, args.eval_episodes)) for d, env_str in enumerate(args.envs)]
     train(agent, envs, eval_envs, args.envs, args.num_steps, eps, args.eval_frequency, args.eval_episodes, policy_path,

@@ -193,11 +193,20 @@ def check_device_drawn_bags(lib, device="cpu"):
         agent.replay_buffer.flush()
         j += 1
     seen_sampled = seen_prefix = 0
+    from oracle import sampler_oracle as S
     for it in range(6):
+        n_valid, exclude = agent.replay_buffer.valid_range()
+        assert int(agent.engine.step_counter[1]) == it          # the optimizer step that keys this update's draws
         agent.train()
         eng, arrays = agent.engine, agent.replay_buffer.export_arrays()
         eps, starts = eng.ep_idx.cpu().numpy(), eng.start.cpu().numpy()
         bo, ba = eng.bag_obs.cpu().numpy(), eng.bag_actions.cpu().numpy()
+        # exactly the oracle's windows and the oracle's rows (oracle/sampler_oracle.py), not just some valid ones
+        we, ws = S.window_draw(arrays["eplens"], n_valid, exclude, cfg.history_len, agent.sample_seed, it, np.arange(meta["B"]))
+        assert np.array_equal(eps, we) and np.array_equal(starts, ws), (it, eps, we, starts, ws)
+        rows = np.stack([S.bag_rows(agent.sample_seed, it, b, ws[b], cfg.bag_size) for b in range(meta["B"])])
+        wo, wa = S.gather_bag(arrays, we, rows, meta["mask"])
+        assert np.array_equal(bo, wo) and np.array_equal(ba, wa), it
         for b in range(meta["B"]):
             ep_obs, ep_act, st = arrays["obss"][eps[b]], arrays["actions"][eps[b]], int(starts[b])
             if st < cfg.bag_size:

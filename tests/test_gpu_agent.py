@@ -55,6 +55,7 @@ def test_device_sampler_distribution():
     """dtqn_replay_sample draws episodes uniformly over finished slots minus the one in progress and starts
     uniformly on {0..max(0, len-L)} (replay_buffer.py:141-158)."""
     import run as runpy
+    from oracle.sampler_oracle import window_draw
     env, agent = _agent(2, sampler="device", sample_seed=5)
     runpy.prepopulate(agent, 9000, [env])
     rb, eng = agent.replay_buffer, agent.engine
@@ -68,6 +69,9 @@ def test_device_sampler_distribution():
         e, s = eng.ep_idx.cpu().numpy(), eng.start.cpu().numpy()
         assert (e >= 0).all() and (e < n_valid).all() and (e != exclude).all()
         assert (s >= 0).all() and (s <= np.maximum(0, lens[e] - 50)).all()
+        # every draw is the oracle's (oracle/sampler_oracle.py), whose distribution tests/test_sampler_reference.py holds to the reference's
+        we, ws = window_draw(lens, n_valid, exclude, 50, 5, it, np.arange(32))
+        assert np.array_equal(e, we) and np.array_equal(s, ws), it
         np.add.at(counts, e, 1)
     skip = exclude < n_valid                 # the in-progress slot only lies inside [0, n_valid) once the ring has wrapped
     expected = 300 * 32 / (n_valid - (1 if skip else 0))
